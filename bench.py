@@ -18,6 +18,13 @@ docs/PERF.md.
 
 Launch: ``python bench.py`` (1 GPU) or ``torchrun --nproc-per-node N bench.py --gpus N``.
 Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the ``--steps`` fits and prints the line. ``--full`` adds what the
+headline figure does not need: the test-set AUC of the last fit's model and its comparison with the CPU
+reference (``auc*`` fields), and under data parallelism the replica digest check (``replicas_agree``).
+``--dump-outputs DIR`` writes what the last timed fit returned (the model's trees, the quantile cuts, the
+training margins) as ``DIR/<name>.npy``; with the same arguments the inputs, and so these arrays, are the
+same from run to run.
 """
 from __future__ import annotations
 
@@ -58,6 +65,45 @@ PARITY_AUC = {
 }
 PARITY_TOL = 0.002
 
+DUMP_MARGIN_ROWS = 12_000_000  # training margins written whole up to here (48 MB of float32), sampled beyond
+DUMP_SAMPLE_ROWS = 4_000_000   # ... to 16 MB of margins + 32 MB of float64 row indices
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir: str, booster, rep) -> None:
+    """What a caller of the timed fit receives, as ``<out_dir>/<name>.npy`` (float32 / float64, < 64 MB in
+    all): every tree's node arrays concatenated in tree order (``tree_offsets`` delimits them), the
+    quantile cuts and bin counts the fit sketched, and this rank's training margins after the last tree
+    (when the shard has more than ``DUMP_MARGIN_ROWS`` rows, a fixed seeded sample of ``DUMP_SAMPLE_ROWS``
+    of them, whose indices ``margin_rows`` holds)."""
+    import numpy as np
+    from pathlib import Path
+
+    def host(v):
+        return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+
+    def floating(v):  # integers to float64 (exact), float32 / float64 as they are
+        v = host(v)
+        return v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    trees = booster.trees
+    arrays = {"tree_offsets": np.cumsum([0] + [t.num_nodes for t in trees])}
+    for name in ("left_children", "right_children", "parents", "split_indices", "split_conditions",
+                 "default_left", "base_weights", "loss_changes", "sum_hessian"):
+        arrays[name] = np.concatenate([getattr(t, name) for t in trees]) if trees else np.zeros(0, np.float32)
+    arrays["cuts"] = rep.extra["cuts"]
+    arrays["nbins"] = rep.extra["nbins"]
+    margin = rep.extra["margin"]
+    if margin.shape[0] > DUMP_MARGIN_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(margin.shape[0], DUMP_SAMPLE_ROWS, replace=False))
+        arrays["margin_rows"] = rows
+        margin = margin[torch.as_tensor(rows, device=margin.device)] if isinstance(margin, torch.Tensor) else margin[rows]
+    arrays["margin"] = margin
+    for name, v in arrays.items():
+        np.save(out / f"{name}.npy", floating(v))
+
 
 def main() -> None:
     ap = argparse.ArgumentParser()
@@ -76,6 +122,11 @@ def main() -> None:
                          "(XGBoost hist's all-row semantics; csrc/sketch.hip)")
     ap.add_argument("--grad-bits", type=int, default=17, choices=[17, 25],
                     help="fixed-point gradient bits: 17 (packed u64 histogram cells, default) or 25 (int64 cells)")
+    ap.add_argument("--full", action="store_true",
+                    help="also score the test rows (AUC, parity with the CPU reference) and, under data "
+                         "parallelism, compare the ranks' model digests")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed fit's outputs (trees, cuts, training margins) as DIR/<name>.npy")
     a = ap.parse_args()
 
     from cobalt_smart_lender_ai_amd.dataio import synth
@@ -153,8 +204,11 @@ def main() -> None:
 
     # (outside the timed region) data parallel: every rank must hold the same model -- a 52-bit digest
     # of the last fit's UBJSON, compared by a min / max all-reduce
+    if a.dump_outputs and rank == 0 and booster is not None:
+        dump_outputs(a.dump_outputs, booster, reps[-1])
+
     replicas_agree = None
-    if world > 1 and booster is not None:
+    if a.full and world > 1 and booster is not None:
         import hashlib
 
         h = float(int.from_bytes(hashlib.sha256(booster.save_raw("ubj")).digest()[:8], "little") >> 12)
@@ -163,11 +217,11 @@ def main() -> None:
             print("[bench] ERROR: data-parallel ranks hold different models", file=sys.stderr)
 
     auc = None
-    if rank == 0 and booster is not None:
+    if a.full and rank == 0 and booster is not None:
         Xt, yt = synth.make_lendingclub(a.test_rows, seed=a.seed, row_offset=n_global, device=dev)
         p = booster.predict_proba(Xt, device=dev)
         auc = float(roc_auc(yt, p))
-    parity = PARITY_AUC.get((n_global, a.trees, a.depth, a.seed, a.test_rows))
+    parity = PARITY_AUC.get((n_global, a.trees, a.depth, a.seed, a.test_rows)) if a.full else None
     parity_ref = parity["auc"] if parity else None
     auc_parity_ok = None if (auc is None or parity_ref is None) else abs(auc - parity_ref) <= PARITY_TOL
     if auc_parity_ok is False:

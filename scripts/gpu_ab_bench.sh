@@ -8,7 +8,7 @@ for k in $(seq 1 ${ROUNDS:-2}); do
   for rows in ${BENCH_ROWS:-10000000 1250000}; do
     for spec in "$@"; do
       name=${spec%%=*}; e=$(envof "${spec#*=}")
-      line=$(env $e timeout -k 10 200 python bench.py --rows $rows --steps ${STEPS:-5} --warmup 2 --test-rows 100000 \
+      line=$(env $e timeout -k 10 200 python bench.py --rows $rows --steps ${STEPS:-5} --warmup 2 --test-rows 100000 --full \
              2>/dev/null | grep '^{') || exit 1
       echo "$name rows=$rows $(python -c "import json,sys; d=json.loads(sys.argv[1]); print(d['ms_per_step'], d['auc'], d['fit_breakdown_ms']['boost'])" "$line")"
     done

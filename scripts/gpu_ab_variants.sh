@@ -16,7 +16,7 @@ for k in 1 2; do
   for spec in "$@"; do
     name=${spec%%=*}; e=$(envof "${spec#*=}")
     for rows in ${BENCH_ROWS:-10000000}; do
-      line=$(env $e timeout -k 10 200 python bench.py --rows $rows --steps 3 --warmup 1 2>/dev/null | grep '^{') || exit 1
+      line=$(env $e timeout -k 10 200 python bench.py --rows $rows --steps 3 --warmup 1 --full 2>/dev/null | grep '^{') || exit 1
       echo "$name rows=$rows $(python -c "import json,sys; d=json.loads(sys.argv[1]); print(d['ms_per_step'], d['auc'])" "$line")"
     done
   done

@@ -12,7 +12,7 @@ for x in "$@"; do
 done
 for k in 1 2; do
   for x in "$@"; do
-    line=$(env $V=$x timeout -k 10 200 python bench.py --rows ${BENCH_ROWS:-10000000} --steps 3 --warmup 1 2>/dev/null | grep '^{') || exit 1
+    line=$(env $V=$x timeout -k 10 200 python bench.py --rows ${BENCH_ROWS:-10000000} --steps 3 --warmup 1 --full 2>/dev/null | grep '^{') || exit 1
     echo "$V=$x $(python -c "import json,sys; d=json.loads(sys.argv[1]); print(d['ms_per_step'], d['auc'])" "$line")"
   done
 done

@@ -38,7 +38,7 @@ for step in "$@"; do
       bash $S ${tag}_smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
       echo "$tag smoke: $(grep -c 'smoke ok' gpurun_out/${tag}_smoke.log)" >> $OUT ;;
     bench)
-      bash $S ${tag}_bench 300 python bench.py --steps 5 --warmup 2 $BENCH_ARGS || exit $?
+      bash $S ${tag}_bench 300 python bench.py --steps 5 --warmup 2 --full $BENCH_ARGS || exit $?
       echo "$tag bench10M: $(ms gpurun_out/${tag}_bench.log) ms auc $(auc gpurun_out/${tag}_bench.log)" >> $OUT ;;
     shards)
       for r in ${SHARD_ROWS:-5000000 2500000 1250000 1000000}; do

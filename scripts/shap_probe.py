@@ -25,7 +25,7 @@ def main() -> None:
     sizes = [int(a) for a in sys.argv[1:]] or [64, 512, 4096, 65535]
     if os.environ.get("SHAP_TABLE_MIN"):
         predict_ops.SHAP_ROWS_MIN = int(os.environ["SHAP_TABLE_MIN"])
-    b = load_pickle_bytes((ROOT / "tests" / "fixtures" / "xgb_model_tree.pkl").read_bytes())[1]
+    b = load_pickle_bytes((ROOT / "src" / "api" / "models" / "xgb_model_tree.pkl").read_bytes())[1]
     dev = torch.device("cuda", 0)
     F = b.num_feature
     X, _ = synth.make_lendingclub(max(sizes), seed=5, device=dev)

@@ -1,3 +1,4 @@
+import lzma
 import os
 import sys
 from pathlib import Path
@@ -6,7 +7,9 @@ import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-REFERENCE_PKL = Path(os.environ.get("COBALT_REFERENCE_PKL", "/root/reference/src/api/models/xgb_model_tree.pkl"))
+GOLDEN = ROOT / "tests" / "golden"
+# the reference's shipped model: the stored copy (xz of the identical bytes), or COBALT_REFERENCE_PKL
+REFERENCE_PKL = os.environ.get("COBALT_REFERENCE_PKL", "")
 
 
 def pytest_configure(config):
@@ -29,11 +32,10 @@ def pytest_collection_modifyitems(config, items):
 
 @pytest.fixture(scope="session")
 def reference_model_bytes():
-    """The shipped reference checkpoint, or the in-repo copy made by tests/fixtures (read as bytes only)."""
-    for p in (REFERENCE_PKL, ROOT / "tests" / "fixtures" / "xgb_model_tree.pkl"):
-        if p.exists():
-            return p.read_bytes()
-    pytest.skip("reference checkpoint not available")
+    """The shipped reference checkpoint (read as bytes only): tests/golden/xgb_model_tree.pkl.xz."""
+    if REFERENCE_PKL:
+        return Path(REFERENCE_PKL).read_bytes()
+    return lzma.decompress((GOLDEN / "xgb_model_tree.pkl.xz").read_bytes())
 
 
 @pytest.fixture(scope="session")

@@ -17,7 +17,7 @@ ROOT = Path(__file__).resolve().parents[1]
 # summaries, which are within the summary's rank error of the 1-rank cuts but not equal to them; the
 # GPU's all-row sketch is exact under DP -- tests/test_00gpu_dp_ipc.py)
 ARGS = ["--rows", "200000", "--trees", "5", "--steps", "1", "--warmup", "0", "--test-rows", "50000",
-        "--sketch-rows", "65536"]
+        "--sketch-rows", "65536", "--full"]
 
 
 def _env():

@@ -6,7 +6,7 @@ import pytest
 from cobalt_smart_lender_ai_amd.dataio import datasets, dvc
 from cobalt_smart_lender_ai_amd.dataio.artifacts import LocalStore
 
-REF = Path("/root/reference")
+REF = Path(__file__).parent / "golden" / "reference_dvc"  # the reference's two .dvc pointers and .dvc/config
 
 
 def test_read_config_format(tmp_path):
@@ -18,16 +18,16 @@ def test_read_config_format(tmp_path):
     assert cfg["remotes"]["myremote"]["url"] == datasets.DVC_REMOTE
 
 
-def test_reference_pointers_match_the_manifest():
-    ptrs = sorted(REF.glob("data/1-raw/lending-club-2007-2020Q3/*.dvc"))
-    if not ptrs:
-        pytest.skip("reference pointers not available")
+def test_reference_pointers_match_the_manifest(tmp_path):
+    ptrs = sorted(REF.glob("*.dvc"))
+    assert len(ptrs) == 2
     outs = {o.path: o for p in ptrs for o in dvc.read_pointer(p)}
     for f in datasets.RAW_MANIFEST:
         o = outs[Path(f.path).name]
         assert (o.md5, o.size, o.hash) == (f.md5, f.size, "md5")
-    if (REF / ".dvc" / "config").exists():
-        assert dvc.read_config(REF)["remotes"]["myremote"]["url"] == datasets.DVC_REMOTE
+    (tmp_path / ".dvc").mkdir()
+    (tmp_path / ".dvc" / "config").write_bytes((REF / "config").read_bytes())
+    assert dvc.read_config(tmp_path)["remotes"]["myremote"]["url"] == datasets.DVC_REMOTE
 
 
 def test_add_status_push_pull_round_trip(tmp_path):

@@ -63,7 +63,7 @@ def test_torchrun_bench_on_every_gpu():
         pytest.skip("needs >= 2 GPUs")
     if torch.cuda.is_initialized():
         pytest.skip("HIP already initialised in this process; run this file on its own")
-    common = ["--rows", "1000000", "--steps", "1", "--warmup", "1", "--test-rows", "100000"]
+    common = ["--rows", "1000000", "--steps", "1", "--warmup", "1", "--test-rows", "100000", "--full"]
     env = {**os.environ, "MASTER_ADDR": "127.0.0.1"}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
                         "--master-addr", "127.0.0.1", "--master-port", "29631", "bench.py", "--gpus", str(n), *common],

@@ -15,7 +15,7 @@ ROOT = Path(__file__).resolve().parents[1]
 @pytest.mark.timeout(300)
 def test_bench_prints_one_contract_json_line():
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--rows", "200000", "--trees", "5", "--steps", "2",
-                          "--warmup", "1", "--test-rows", "20000"], cwd=ROOT, capture_output=True, text=True,
+                          "--warmup", "1", "--test-rows", "20000", "--full"], cwd=ROOT, capture_output=True, text=True,
                          timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -43,7 +43,7 @@ def test_torchrun_one_rank_equals_plain_bench():
     from cobalt_smart_lender_ai_amd.parallel.dp_check import free_port
 
     args = ["bench.py", "--gpus", "1", "--rows", "1000000", "--trees", "20", "--steps", "1", "--warmup", "1",
-            "--test-rows", "100000"]
+            "--test-rows", "100000", "--full"]
     plain = subprocess.run([sys.executable, *args], cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert plain.returncode == 0, plain.stderr[-2000:]
     tr = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
@@ -64,7 +64,7 @@ def test_bench_auc_matches_the_pinned_host_oracle():
     the synthetic rows come from the device generator here, the host one there) and the JSON names the
     reference's source (bench.py PARITY_AUC)."""
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--rows", "100000", "--test-rows", "100000",
-                          "--steps", "1", "--warmup", "0"], cwd=ROOT, capture_output=True, text=True, timeout=280)
+                          "--steps", "1", "--warmup", "0", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
     assert "host trainer" in d["auc_parity_source"], d

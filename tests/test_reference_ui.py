@@ -26,7 +26,7 @@ import pytest
 REF_UI = Path(os.environ.get("COBALT_REFERENCE_UI", "/root/reference/src/streamlit_ui/cobalt_streamlit.py"))
 HOST = "http://cobalt-lender-api:8000"
 
-FIXTURE = Path(__file__).parent / "fixtures" / "reference_ui_exchanges.json"
+FIXTURE = Path(__file__).parent / "golden" / "reference_ui_exchanges.json"
 needs_ref = pytest.mark.skipif(not REF_UI.exists(), reason="reference UI script not available")
 
 
@@ -193,7 +193,7 @@ def _close(a, b, path=""):
 @needs_ref
 def test_reference_ui_exchanges_fixture_is_current(monkeypatch, reference_booster):
     """The reference UI's HTTP exchanges (both modes) against the host engine, recorded into
-    tests/fixtures/reference_ui_exchanges.json: the requests the unmodified script sends and the
+    tests/golden/reference_ui_exchanges.json: the requests the unmodified script sends and the
     responses it renders (p = 9.42%). Where the reference checkout exists this asserts the fixture is
     current; COBALT_RECORD_UI=1 rewrites it."""
     import requests
