@@ -18,6 +18,7 @@
 // are reduced per block in LDS and flushed with one fp64 atomic per (row, feature).
 #include "common.h"
 #include "knobs.h"
+#include "shap_paths.h"
 #include <algorithm>
 
 using namespace cobalt;
@@ -28,7 +29,6 @@ namespace {
 // per-block LDS footprint low -> more resident blocks per CU, which is what bounds this
 // latency-bound walk: 125M-row scoring went 490M (6144-node tiles) -> 810M rows/s (2048).
 constexpr int kMaxTileNodes = 8192;
-constexpr int kMaxPath = 16;       // max unique elements per path (incl. bias) in the SHAP kernel
 }
 
 // ------------------------------------------------------------------------------------ predictor
@@ -208,27 +208,7 @@ COBALT_API int cobalt_predict_small(const float* X, int64_t n, int F, int64_t ld
 }
 
 // ------------------------------------------------------------------------------------ TreeSHAP
-struct PathElem {
-  float lo, hi;        // row follows the path on this feature iff lo <= x < hi (non-missing)
-  int32_t feat;        // feature index
-  int32_t nan_ok;      // row with NaN follows the path on this feature
-  double zero;         // product of cover(child)/cover(parent) over the merged occurrences
-};
-static_assert(sizeof(PathElem) == 24, "PathElem");
-
-// EXTEND / UNWIND without per-step divisions: the integer ratios (j + 1) / (l + 1) fold to constants of
-// the unrolled loops, 1 / (k - j) comes from kShapInv and 1 / zero is taken once per element; both SHAP
-// kernels (and so the pattern tables) use the same operation order, so their values stay bit-identical
-// to each other (and within rounding of the division form and of the host oracle).
-__constant__ double kShapInv[18] = {0.0,       1.0,        1.0 / 2,  1.0 / 3,  1.0 / 4,  1.0 / 5,
-                                    1.0 / 6,   1.0 / 7,    1.0 / 8,  1.0 / 9,  1.0 / 10, 1.0 / 11,
-                                    1.0 / 12,  1.0 / 13,   1.0 / 14, 1.0 / 15, 1.0 / 16, 1.0 / 17};
-
-// Canonical summation order (shared by both SHAP kernels, so a row's values do not depend on the
-// batch size or on which kernel ran): paths are cut into fixed chunks of kShapChunk; within a chunk
-// contributions are added in path order; k_shap_reduce adds the chunk sums in chunk order. No
-// floating-point atomics anywhere.
-constexpr int kShapChunk = 256;
+// PathElem, kShapInv and the canonical summation order (kShapChunk): shap_paths.h
 constexpr int kShapMaxF = 80;  // path-parallel kernel: [kShapChunk][F] doubles of LDS
 
 // Path-parallel kernel (small batches): block = (chunk, row), one path per thread; each thread

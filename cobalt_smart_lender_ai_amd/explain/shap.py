@@ -36,6 +36,16 @@ class TreeExplainer:
         phi = self.booster.shap_values(Xn, device=self.device)
         return np.asarray(phi.cpu().numpy() if hasattr(phi, "cpu") else phi, dtype=np.float64)
 
+    def shap_interaction_values(self, X) -> np.ndarray:
+        """``shap.TreeExplainer.shap_interaction_values``: [N, F, F] float64; a DataFrame's columns are
+        reordered by feature name."""
+        names = self.booster.feature_names
+        if hasattr(X, "columns") and names:
+            X = X[names]
+        Xn = X.to_numpy(dtype=np.float32, na_value=np.nan) if hasattr(X, "to_numpy") else np.asarray(X, np.float32)
+        out = self.booster.shap_interaction_values(Xn, device=self.device)
+        return np.asarray(out.cpu().numpy() if hasattr(out, "cpu") else out, dtype=np.float64)
+
     def __call__(self, X) -> "Explanation":
         vals = self.shap_values(X)
         data = X.to_numpy(dtype=np.float64, na_value=np.nan) if hasattr(X, "to_numpy") else np.asarray(X, np.float64)
@@ -108,3 +118,20 @@ def force_data(exp: Explanation, i: int) -> dict:
     return {"base_value": float(exp.base_values[i]), "output": float(exp.base_values[i] + v.sum()),
             "contributions": [{"feature": exp.feature_names[j], "value": float(exp.data[i, j]),
                                "shap": float(v[j])} for j in order]}
+
+
+def top_interactions(values, feature_names, k: int = 10) -> list[dict]:
+    """The ``k`` strongest feature pairs of interaction values [N, F, F] (or one matrix [F, F]):
+    strength = mean over rows of ``|Phi[i][j] + Phi[j][i]|`` for i < j, strongest first, ties in
+    (i, j) order."""
+    v = np.asarray(values, dtype=np.float64)
+    if v.ndim == 2:
+        v = v[None]
+    F = v.shape[1]
+    if v.shape[2] != F or len(feature_names) != F:
+        raise ValueError(f"expected [N, F, F] values and F feature names, got {v.shape} and {len(feature_names)}")
+    iu, ju = np.triu_indices(F, 1)
+    strength = np.abs(v[:, iu, ju] + v[:, ju, iu]).mean(0) if v.shape[0] else np.zeros(len(iu))
+    order = np.argsort(-strength, kind="stable")[:k]
+    return [{"feature_a": feature_names[iu[q]], "feature_b": feature_names[ju[q]], "strength": float(strength[q])}
+            for q in order]

@@ -7,9 +7,10 @@ per-tree arrays (``left_children``, ``right_children``, ``parents``, ``split_ind
 ``split_conditions``, ``default_left``, ``base_weights``, ``loss_changes``, ``sum_hessian``) and
 reads/writes that document, so artifacts move both ways between this framework and XGBoost.
 
-Inference (`predict`, `shap_values`) dispatches on device: CUDA tensors / ``device="cuda"`` run the
-gfx950 kernels in ``ops/predict_ops.py``; ``device="cpu"`` runs the NumPy reference implementation
-(`predict_margin_host`, `treeshap_host`), which is also the oracle of the GPU tests.
+Inference (`predict`, `shap_values`, `shap_interaction_values`) dispatches on device: CUDA tensors /
+``device="cuda"`` run the gfx950 kernels in ``ops/predict_ops.py``; ``device="cpu"`` runs the NumPy
+reference implementation (`predict_margin_host`, `treeshap_host`, `treeshap_interactions_host`), which is
+also the oracle of the GPU tests.
 """
 from __future__ import annotations
 
@@ -202,6 +203,14 @@ class Booster:
         from ..ops import predict_ops
 
         return predict_ops.shap_values(self, X, device=device)
+
+    def shap_interaction_values(self, X, device: str | None = None):
+        """Path-dependent TreeSHAP interaction values [N, F, F] float64: every row of a matrix sums to
+        the feature's SHAP value, off-diagonal cells split a pairwise effect evenly between [i][j] and
+        [j][i], the diagonal holds the main effects."""
+        from ..ops import predict_ops
+
+        return predict_ops.shap_interaction_values(self, X, device=device)
 
     def expected_value(self) -> float:
         """TreeExplainer ``expected_value``: base margin + cover-weighted mean leaf value per tree."""
@@ -539,6 +548,153 @@ def iter_leaf_paths(t: Tree) -> Iterable[tuple[int, list[tuple[int, int, bool]]]
         f = int(t.split_indices[j])
         stack.append((int(t.right_children[j]), path + [(j, f, False)]))
         stack.append((int(t.left_children[j]), path + [(j, f, True)]))
+
+
+def merged_leaf_paths(t: Tree) -> Iterable[tuple[float, list[tuple[int, np.float32, np.float32, bool, float]]]]:
+    """Yield (leaf value, [(feature, lo, hi, nan_ok, zero fraction)]) per leaf path with the splits on
+    one feature merged into one element: a row follows the element iff ``lo <= x < hi`` (NaN: iff
+    every merged split sends missing values this way); the zero fraction is the product of the
+    cover ratios of the merged splits. Elements are in order of first occurrence."""
+    cov = t.sum_hessian.astype(np.float64)
+    for leaf, path in iter_leaf_paths(t):
+        merged: dict[int, list] = {}
+        for node, f, went_left in path:
+            child = int(t.left_children[node] if went_left else t.right_children[node])
+            m = merged.setdefault(f, [np.float32(-np.inf), np.float32(np.inf), True, 1.0])
+            thr = t.split_conditions[node]
+            if went_left:
+                m[1] = min(m[1], thr)
+            else:
+                m[0] = max(m[0], thr)
+            m[2] = m[2] and (bool(t.default_left[node]) == went_left)
+            m[3] *= cov[child] / cov[node]
+        yield float(t.split_conditions[leaf]), [(f, *m) for f, m in merged.items()]
+
+
+def _paths_by_length(b: Booster) -> list[tuple[int, tuple]]:
+    """The merged leaf paths of all trees grouped by their number of elements k >= 1, as arrays
+    (leaf [P], feature / lo / hi / nan_ok / zero [P, k]); kept with the booster while its trees stay."""
+    cache = b.__dict__.setdefault("_host_path_cache", {})
+    key = tuple(id(t) for t in b.trees)
+    if cache.get("key") != key:
+        by_len: dict[int, list] = {}
+        for t in b.trees:
+            for leaf, elems in merged_leaf_paths(t):
+                by_len.setdefault(len(elems), []).append((leaf, elems))
+        groups = []
+        for k, paths in sorted(by_len.items()):
+            if k == 0:
+                continue
+            col = lambda c, dt: np.array([[e[c] for e in p[1]] for p in paths], dtype=dt)  # noqa: E731
+            groups.append((k, (np.array([p[0] for p in paths], dtype=np.float64), col(0, np.int64),
+                               col(1, np.float32), col(2, np.float32), col(3, bool), col(4, np.float64))))
+        cache.update(key=key, groups=groups)
+    return cache["groups"]
+
+
+def _extend_sum(z: list, o: list) -> Any:
+    """Sum of the permutation weights EXTEND builds over elements with zero / one fractions ``z`` / ``o``
+    (arrays broadcast against each other): sum_S |S|! (m - |S|)! / (m + 1)! prod_{S} o prod_{not S} z."""
+    w = [1.0]
+    for l, (ze, oe) in enumerate(zip(z, o), start=1):
+        w.append(0.0)
+        for j in range(l - 1, -1, -1):
+            w[j + 1] = w[j + 1] + oe * w[j] * ((j + 1) / (l + 1))
+            w[j] = ze * w[j] * ((l - j) / (l + 1))
+    tot = w[0]
+    for x in w[1:]:
+        tot = tot + x
+    return tot
+
+
+def treeshap_interactions_host(b: Booster, X: np.ndarray) -> np.ndarray:
+    """Path-dependent TreeSHAP interaction values [N, F, F] float64 in margin space (covers =
+    ``sum_hessian``): ``shap.TreeExplainer.shap_interaction_values``; CPU path of
+    :meth:`Booster.shap_interaction_values` and oracle of the GPU kernel.
+
+    Per merged leaf path (elements e with zero fraction z_e, one fraction o_e, leaf value v):
+    ``Phi[i][j] += v/2 (o_i - z_i)(o_j - z_j) W(path \\ {i, j})`` and ``phi[i] += v (o_i - z_i) W(path \\ {i})``
+    with W the EXTEND weight sum over the remaining elements; ``Phi[i][i] = phi[i] - sum_{j != i}
+    Phi[i][j]``. Vectorised over rows and over the paths of equal length."""
+    X = np.asarray(X, dtype=np.float32)
+    N, F = X.shape
+    upper = np.zeros((N, F * F), dtype=np.float64)   # cell (min(i, j), max(i, j)) of every pair
+    phi = np.zeros((N, F), dtype=np.float64)
+    rows = np.arange(N)[:, None]
+    for k, (v, feat, lo, hi, nan_ok, zero) in _paths_by_length(b):
+        xv = X[:, feat]                                                             # [N, P, k]
+        one = np.where(np.isnan(xv), nan_ok, (xv >= lo) & (xv < hi)).astype(np.float64)
+        z = [zero[:, e] for e in range(k)]
+        o = [one[:, :, e] for e in range(k)]
+        for a in range(k):
+            rest = [e for e in range(k) if e != a]
+            val = v * (o[a] - z[a]) * _extend_sum([z[e] for e in rest], [o[e] for e in rest])
+            np.add.at(phi, (rows, feat[:, a][None, :]), val)
+            for c in range(a + 1, k):
+                rest = [e for e in range(k) if e != a and e != c]
+                val = 0.5 * v * ((o[a] - z[a]) * (o[c] - z[c])) * _extend_sum([z[e] for e in rest],
+                                                                               [o[e] for e in rest])
+                fa, fc = feat[:, a], feat[:, c]
+                cell = np.minimum(fa, fc) * F + np.maximum(fa, fc)
+                np.add.at(upper, (rows, cell[None, :]), val)
+    upper = upper.reshape(N, F, F)
+    out = upper + upper.transpose(0, 2, 1)
+    d = np.arange(F)
+    out[:, d, d] = phi - out.sum(2)
+    return out
+
+
+def shapley_interactions_bruteforce(b: Booster, X: np.ndarray) -> np.ndarray:
+    """Shapley interaction values [N, F, F] by the definition, for tests on tiny models (F <= 6):
+    every subset S is evaluated with the conditional expectation f_x(S) of Lundberg et al.,
+    Algorithm 1 (EXPVALUE: follow x at splits on features of S, NaN by the default direction, else
+    the cover-weighted mean of both children), by recursion on the raw trees. No paths, no EXTEND."""
+    from itertools import combinations
+
+    X = np.asarray(X, dtype=np.float32)
+    N, F = X.shape
+    if F > 6:
+        raise ValueError("brute-force interaction values are for F <= 6")
+    fact = [math.factorial(i) for i in range(F + 1)]
+
+    def expvalue(t: Tree, cov, j: int, x, S: frozenset) -> float:
+        if t.left_children[j] == -1:
+            return float(t.split_conditions[j])
+        f = int(t.split_indices[j])
+        l, r = int(t.left_children[j]), int(t.right_children[j])
+        if f in S:
+            v = x[f]
+            left = bool(t.default_left[j]) if np.isnan(v) else bool(v < t.split_conditions[j])
+            return expvalue(t, cov, l if left else r, x, S)
+        return (cov[l] * expvalue(t, cov, l, x, S) + cov[r] * expvalue(t, cov, r, x, S)) / cov[j]
+
+    covs = [t.sum_hessian.astype(np.float64) for t in b.trees]
+    out = np.zeros((N, F, F), dtype=np.float64)
+    for n in range(N):
+        fx = {}
+        for size in range(F + 1):
+            for S in combinations(range(F), size):
+                S = frozenset(S)
+                fx[S] = sum(expvalue(t, c, 0, X[n], S) for t, c in zip(b.trees, covs))
+        phi = np.zeros(F)
+        for i in range(F):
+            others = [f for f in range(F) if f != i]
+            for size in range(F):
+                for S in combinations(others, size):
+                    S = frozenset(S)
+                    phi[i] += fact[size] * fact[F - size - 1] / fact[F] * (fx[S | {i}] - fx[S])
+            for j in range(F):
+                if j == i:
+                    continue
+                rest = [f for f in others if f != j]
+                for size in range(F - 1):
+                    for S in combinations(rest, size):
+                        S = frozenset(S)
+                        wgt = fact[size] * fact[F - size - 2] / (2 * fact[F - 1])
+                        out[n, i, j] += wgt * (fx[S | {i, j}] - fx[S | {i}] - fx[S | {j}] + fx[S])
+        for i in range(F):
+            out[n, i, i] = phi[i] - (out[n, i].sum() - out[n, i, i])
+    return out
 
 
 def trees_from_heap_nodes(nodes: np.ndarray, max_depth: int, native: bool | None = None) -> list[Tree]:

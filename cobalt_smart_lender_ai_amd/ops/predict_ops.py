@@ -13,7 +13,8 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..models.booster import Booster, Tree, predict_margin_host, sigmoid32, treeshap_host
+from ..models.booster import (Booster, Tree, predict_margin_host, sigmoid32, treeshap_host,
+                              treeshap_interactions_host)
 from ..config import knob
 
 # LDS tile capacity in nodes: a model's tile is max(this, its largest tree), at most MAX_TILE_NODES
@@ -50,6 +51,17 @@ SHAP_ROWS_MIN = 256  # batches from this size use the row-parallel table kernel
 SHAP_ROWS_MAX_F = 48
 SHAP_TABLE_MAX_K = 10             # longest path (unique features) that gets a pattern table
 SHAP_TABLE_MAX_BYTES = 2 << 30    # per-model table budget on the device
+
+_native.register("cobalt_treeshap_interactions", ctypes.c_int,
+                 [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p])
+_native.register("cobalt_treeshap_interactions_max_f", ctypes.c_int, [])
+_native.register("cobalt_treeshap_interactions_lds", ctypes.c_int64, [ctypes.c_int, ctypes.c_int])
+SHAP_INT_MAX_F = 48            # widest model of the interaction kernel (csrc/shapint.hip kShapIntMaxF)
+# Rows per launch of the interaction values: bounds the scratch of the SHAP values they start from
+# (phi [rows, F] plus treeshap_gpu's [rows, chunks, F] slab: 16384 x 117 x 20 doubles = 307 MB for the
+# shipped model); the interaction kernel itself keeps its accumulators in LDS and has no global scratch.
+SHAP_INT_ROWS = 16384
 
 PATH_ELEM = np.dtype([("lo", "<f4"), ("hi", "<f4"), ("feat", "<i4"), ("nan_ok", "<i4"), ("zero", "<f8")])
 
@@ -313,3 +325,45 @@ def shap_values(b: Booster, X, device=None):
         return phi if isinstance(X, torch.Tensor) else phi.cpu().numpy()
     Xn = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
     return treeshap_host(b, Xn)
+
+
+# tests run the long-path kernel variant on models whose paths would take the short-path one
+_FORCE_LONG_PATH_INTERACTIONS = False
+
+
+def treeshap_interactions_gpu(b: Booster, X: torch.Tensor, out: torch.Tensor) -> None:
+    """Write TreeSHAP interaction values into ``out`` [N, F, F] float64 on the current stream
+    (deterministic like :func:`treeshap_gpu`: a row's values do not depend on the batch). Raises
+    ``ValueError`` before anything is launched when the model is outside the kernel's limits."""
+    N, F = X.shape
+    if F < b.num_feature:
+        raise ValueError(f"X has {F} features, model needs {b.num_feature}")
+    if F > SHAP_INT_MAX_F:
+        raise ValueError(f"{F} features exceed the GPU TreeSHAP interaction limit of {SHAP_INT_MAX_F} features")
+    if tuple(out.shape) != (N, F, F) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float64 [{N}, {F}, {F}] tensor")
+    if N == 0:
+        return
+    gf = gpu_forest(b, X.device, None, with_shap=True)  # (raises ValueError past MAX_PATH features per path)
+    lib = _native.lib()
+    max_len = MAX_PATH if _FORCE_LONG_PATH_INTERACTIONS else gf.max_len
+    for s in range(0, N, SHAP_INT_ROWS):
+        e = min(N, s + SHAP_INT_ROWS)
+        phi = torch.zeros((e - s, F), dtype=torch.float64, device=X.device)
+        treeshap_gpu(b, X[s:e], phi)
+        rc = lib.cobalt_treeshap_interactions(X[s:e].data_ptr(), e - s, F, X.stride(0), gf.elems.data_ptr(),
+                                              gf.path_ptr.data_ptr(), gf.path_val.data_ptr(), gf.n_paths,
+                                              max_len, phi.data_ptr(), out[s:e].data_ptr(),
+                                              _native.stream_handle())
+        _native.check(rc, "cobalt_treeshap_interactions")
+
+
+def shap_interaction_values(b: Booster, X, device=None):
+    d = _device_of(X, device)
+    if d.type == "cuda":
+        Xt = _as_f32(X, d)
+        out = torch.empty((Xt.shape[0], Xt.shape[1], Xt.shape[1]), dtype=torch.float64, device=d)
+        treeshap_interactions_gpu(b, Xt, out)
+        return out if isinstance(X, torch.Tensor) else out.cpu().numpy()
+    Xn = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
+    return treeshap_interactions_host(b, Xn)

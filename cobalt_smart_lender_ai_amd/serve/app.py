@@ -6,6 +6,9 @@ Routes (identical paths, request schemas, response keys and error codes):
   ``"application_type_Joint App"`` / ``"hardship_status_No Hardship"``) ->
   ``{prob_default, shap_values[20], base_value, features[20], input_row}``; micro-batched onto the
   GPU engine (hipGraph replay of predictor + TreeSHAP).
+* ``POST /explain_interactions``    -- additive: the ``/predict`` body -> ``{features, base_value, shap_values[20],
+  interaction_values[20][20], top_pairs}``: TreeSHAP interaction values of one borrower (every row of the
+  matrix sums to the feature's SHAP value); computed per request on a worker thread, not micro-batched.
 * ``POST /predict_bulk_csv``        -- multipart field ``file`` with a CSV of the 20 columns ->
   ``{"predictions": [row + prob_default]}`` with NaN/inf rendered ``"null"``; errors -> 500
   ``"Bulk prediction failed: ..."``.
@@ -179,6 +182,18 @@ def _score_device(booster: Booster, Xd, lock=None) -> np.ndarray:
         return score_device_matrix(booster, Xd, capture=False).cpu().numpy()
 
 
+def _interaction_values(booster: Booster, X: np.ndarray, engine=None) -> np.ndarray:
+    """TreeSHAP interaction values [N, F, F] of a few rows: on the local engine's device (serialised
+    with the engine like :func:`_score_device`; no graph capture, no micro-batching), else on the host."""
+    dev = getattr(engine, "device", None)
+    if dev is None or dev.type != "cuda":
+        return np.asarray(booster.shap_interaction_values(X, device="cpu"))
+    import torch
+
+    with engine._lock, torch.cuda.device(dev):
+        return np.asarray(booster.shap_interaction_values(X, device=dev))
+
+
 def create_app(cfg: ServeConfig | None = None, booster: Booster | None = None) -> FastAPI:
     cfg = cfg or from_env(ServeConfig)
     state: dict = {}
@@ -244,6 +259,25 @@ def create_app(cfg: ServeConfig | None = None, booster: Booster | None = None) -
             "base_value": state["expected_value"],
             "features": feats,
             "input_row": {f: float(row[f]) for f in feats},
+        })
+
+    @app.post("/explain_interactions")
+    async def explain_interactions(input_data: SingleInput):
+        from ..explain.shap import top_interactions
+
+        row = input_data.model_dump(by_alias=True)
+        feats = state["features"]
+        X = np.array([[float(row[f]) for f in feats]], dtype=np.float32)
+        engine = None if "remote" in state else state.get("engine")  # remote scorer: this process has no device
+        loop = asyncio.get_running_loop()
+        inter = (await loop.run_in_executor(None, _interaction_values, state["booster"], X, engine))[0]
+        metrics.rows.labels("/explain_interactions").inc()
+        return JSONResponse({
+            "features": feats,
+            "base_value": state["expected_value"],
+            "shap_values": inter.sum(1).tolist(),
+            "interaction_values": inter.tolist(),
+            "top_pairs": top_interactions(inter, feats),
         })
 
     @app.post("/predict_bulk_csv")
