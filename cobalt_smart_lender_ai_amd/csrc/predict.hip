@@ -17,6 +17,7 @@
 // per (row, path) runs EXTEND over the path and the UNWOUND sum per element in fp64, contributions
 // are reduced per block in LDS and flushed with one fp64 atomic per (row, feature).
 #include "common.h"
+#include "forest_walk.h"
 #include "knobs.h"
 #include "shap_paths.h"
 #include <algorithm>
@@ -32,42 +33,7 @@ constexpr int kMaxTileNodes = 8192;
 }
 
 // ------------------------------------------------------------------------------------ predictor
-// A tree walk is a chain of dependent LDS reads (node -> feature value -> next node), so one
-// thread walks kWalk trees at once: the kWalk chains' loads are independent and overlap. The leaf
-// values are still added to the margin one tree at a time in tree order (same fp32 sum).
-// kWalk is the default; COBALT_PRED_WALK=2|8 selects the other instantiations for sweeps.
-constexpr int kWalk = 4;
-
-template <int kWalk = ::kWalk, typename Leaf>
-__device__ __forceinline__ void walk_trees(const uint2* s_nodes, const int32_t* __restrict__ tree_ptr, int nbase,
-                                           int t_begin, int t_end, const float* x, Leaf&& leaf) {
-  for (int t = t_begin; t < t_end; t += kWalk) {
-    uint32_t base[kWalk];
-    uint2 nd[kWalk];
-#pragma unroll
-    for (int k = 0; k < kWalk; ++k) {  // past the tile's end: walk tree t again, result unused
-      base[k] = (uint32_t)(tree_ptr[t + k < t_end ? t + k : t] - nbase);
-      nd[k] = s_nodes[base[k]];
-    }
-    bool more = true;
-    while (more) {
-      more = false;
-#pragma unroll
-      for (int k = 0; k < kWalk; ++k) {
-        if ((nd[k].x & 0xFFFFu) != 0xFFFFu) {
-          const int f = (nd[k].x >> 16) & 0x7FFF;
-          const float v = x[f];
-          const bool left = (v != v) ? ((nd[k].x >> 31) != 0) : (v < __uint_as_float(nd[k].y));
-          nd[k] = s_nodes[base[k] + (nd[k].x & 0xFFFFu) + (left ? 0u : 1u)];
-          more = true;
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kWalk; ++k)
-      if (t + k < t_end) leaf(t + k, __uint_as_float(nd[k].y));
-  }
-}
+// walk_trees (kWalk trees per thread at once, leaf values delivered in tree order): forest_walk.h
 
 template <int W>
 __global__ __launch_bounds__(256) void k_predict(const float* __restrict__ X, int64_t n, int F, int64_t ldx,

@@ -10,7 +10,8 @@ reads/writes that document, so artifacts move both ways between this framework a
 Inference (`predict`, `shap_values`, `shap_interaction_values`) dispatches on device: CUDA tensors /
 ``device="cuda"`` run the gfx950 kernels in ``ops/predict_ops.py``; ``device="cpu"`` runs the NumPy
 reference implementation (`predict_margin_host`, `treeshap_host`, `treeshap_interactions_host`), which is
-also the oracle of the GPU tests.
+also the oracle of the GPU tests. `eval_curve` / `staged_margins` (the metrics / margins after every tree,
+one forest pass; oracle `eval_curve_host`) dispatch the same way.
 """
 from __future__ import annotations
 
@@ -193,10 +194,40 @@ class Booster:
 
         return predict_ops.predict_margin(self, X, device=device, n_trees=n_trees)
 
-    def predict_proba(self, X, device: str | None = None):
+    def predict_proba(self, X, device: str | None = None, n_trees: int | None = None):
         from ..ops import predict_ops
 
-        return predict_ops.predict_proba(self, X, device=device)
+        return predict_ops.predict_proba(self, X, device=device, n_trees=n_trees)
+
+    def eval_curve(self, X, y, sample_weight=None, metrics: Sequence[str] = ("logloss",), device: str | None = None,
+                   margin=None):
+        """The metrics after every tree on the labelled rows ``(X, y)`` in one pass over the forest:
+        ``({metric: float64 [num_trees]}, final margins)``. ``metrics``: "logloss", "error", "auc";
+        ``margin`` ([N] float32): start from these margins instead of the base margin (the trees are then
+        the continuation of the model that produced them)."""
+        from ..ops import predict_ops
+
+        return predict_ops.eval_curve(self, X, y, sample_weight=sample_weight, metrics=metrics, device=device,
+                                      margin=margin)
+
+    def staged_margins(self, X, device: str | None = None):
+        """Margins after every tree, [num_trees, N] float32: row ``t`` has the bits of
+        ``predict_margin(X, n_trees=t + 1)``."""
+        from ..ops import predict_ops
+
+        return predict_ops.staged_margins(self, X, device=device)
+
+    @property
+    def best_iteration(self) -> int | None:
+        """Global index of the best round of an early-stopped fit (XGBoost's ``best_iteration``
+        attribute), None when the model was not fitted with early stopping."""
+        v = self.attributes.get("best_iteration")
+        return int(v) if v is not None else None
+
+    @property
+    def best_score(self) -> float | None:
+        v = self.attributes.get("best_score")
+        return float(v) if v is not None else None
 
     def shap_values(self, X, device: str | None = None):
         """Path-dependent TreeSHAP values [N, F] (+ expected value via :meth:`expected_value`)."""
@@ -437,6 +468,95 @@ def predict_margin_host(b: Booster, X: np.ndarray, n_trees: int | None = None) -
             nid = np.where(active, nxt, nid)
         out = (out + t.split_conditions[nid]).astype(np.float32)
     return out
+
+
+EVAL_METRICS = ("logloss", "error", "auc")
+EVAL_MAXIMIZE = {"logloss": False, "error": False, "auc": True}
+
+
+def check_eval_inputs(n_rows: int, y: np.ndarray, w: np.ndarray | None, metrics: Sequence[str],
+                      margin_rows: int | None = None) -> tuple[str, ...]:
+    """The input checks of :func:`eval_curve_host` / ``predict_ops.eval_curve`` (host arrays; raised
+    before anything is computed or launched). Returns the metrics as a tuple."""
+    metrics = (metrics,) if isinstance(metrics, str) else tuple(metrics)
+    for m in metrics:
+        if m not in EVAL_METRICS:
+            raise ValueError(f"unknown eval metric {m!r}: expected one of {EVAL_METRICS}")
+    if y.ndim != 1 or y.shape[0] != n_rows:
+        raise ValueError(f"X has {n_rows} rows, y has shape {y.shape}")
+    if w is not None and (w.ndim != 1 or w.shape[0] != n_rows):
+        raise ValueError(f"X has {n_rows} rows, sample_weight has shape {w.shape}")
+    if margin_rows is not None and margin_rows != n_rows:
+        raise ValueError(f"X has {n_rows} rows, margin has {margin_rows}")
+    if n_rows and not bool(((y >= 0) & (y <= 1)).all()):  # (NaN fails too)
+        raise ValueError("eval labels must lie in [0, 1]")
+    if w is not None and not bool((w >= 0).all()):
+        raise ValueError("eval sample weights must be non-negative")
+    sw = float(np.sum(w, dtype=np.float64)) if w is not None else float(n_rows)
+    if not sw > 0:
+        raise ValueError("the eval set's weights sum to zero (or it has no rows)")
+    if "auc" in metrics:
+        pos = int((y > 0.5).sum())
+        if pos == 0 or pos == n_rows:
+            raise ValueError("Only one class present in the eval labels: AUC is not defined")
+    return metrics
+
+
+def staged_margins_host(b: Booster, X: np.ndarray, margin: np.ndarray | None = None) -> np.ndarray:
+    """Margins after every tree [num_trees, N] float32, summed as :func:`predict_margin_host` sums them
+    (fp32, tree order), starting from ``margin`` when given."""
+    X = np.asarray(X, dtype=np.float32)
+    N = X.shape[0]
+    cur = (np.full(N, np.float32(b.base_margin), dtype=np.float32) if margin is None
+           else np.asarray(margin, dtype=np.float32).copy())
+    out = np.empty((b.num_trees, N), dtype=np.float32)
+    rows = np.arange(N)
+    for i, t in enumerate(b.trees):
+        nid = np.zeros(N, dtype=np.int32)
+        while N:
+            lc = t.left_children[nid]
+            active = lc != -1
+            if not active.any():
+                break
+            v = X[rows, np.where(active, t.split_indices[nid], 0)]
+            go_left = np.where(np.isnan(v), t.default_left[nid] == 1, v < t.split_conditions[nid])
+            nid = np.where(active, np.where(go_left, lc, t.right_children[nid]), nid)
+        cur = (cur + t.split_conditions[nid]).astype(np.float32)
+        out[i] = cur
+    return out
+
+
+def eval_curve_host(b: Booster, X: np.ndarray, y, sample_weight=None, metrics: Sequence[str] = ("logloss",),
+                    margin: np.ndarray | None = None) -> tuple[dict[str, np.ndarray], np.ndarray]:
+    """NumPy form of :meth:`Booster.eval_curve` (CPU path and oracle of the GPU kernel): the fp32 margin
+    after every tree as :func:`predict_margin_host` sums it, and from that margin ``m`` in float64
+    ``logloss = sum w (log1p(exp(-|m|)) + max(m, 0) - y m) / sum w``, ``error = sum w [(m > 0) != (y > 0.5)]
+    / sum w``; ``auc`` is :func:`~..metrics.auc.roc_auc` of each stage (unweighted)."""
+    X = np.asarray(X, dtype=np.float32)
+    y32 = np.asarray(y, dtype=np.float32).reshape(-1)
+    w32 = None if sample_weight is None else np.asarray(sample_weight, dtype=np.float32).reshape(-1)
+    metrics = check_eval_inputs(X.shape[0], y32, w32, metrics,
+                                None if margin is None else int(np.asarray(margin).shape[0]))
+    stages = staged_margins_host(b, X, margin)
+    yd = y32.astype(np.float64)
+    wd = np.ones_like(yd) if w32 is None else w32.astype(np.float64)
+    sw = wd.sum()
+    ypos = y32 > np.float32(0.5)
+    out = {m: np.empty(b.num_trees, dtype=np.float64) for m in metrics}
+    for t in range(b.num_trees):
+        m = stages[t].astype(np.float64)
+        if "logloss" in out:
+            out["logloss"][t] = np.sum(wd * (np.log1p(np.exp(-np.abs(m))) + np.maximum(m, 0.0) - yd * m)) / sw
+        if "error" in out:
+            out["error"][t] = np.sum(wd * ((stages[t] > 0) != ypos)) / sw
+        if "auc" in out:
+            from ..metrics.auc import roc_auc
+
+            out["auc"][t] = roc_auc(ypos.astype(np.float64), stages[t])
+    final = stages[-1] if b.num_trees else (
+        np.full(X.shape[0], np.float32(b.base_margin), dtype=np.float32) if margin is None
+        else np.asarray(margin, dtype=np.float32).copy())
+    return out, final
 
 
 def sigmoid32(m: np.ndarray) -> np.ndarray:

@@ -125,10 +125,15 @@ class ExternalReport:
 
 def train_external(source: ChunkSource, params: GBDTParams | dict | None = None, *, n_rows: int | None = None,
                    device=None, sample_rate: float = 0.2, device_page_bytes: int = 0, feature_names=None,
-                   feature_types=None, report: ExternalReport | None = None) -> Booster:
+                   feature_types=None, report: ExternalReport | None = None, evals=None, eval_metric=None,
+                   early_stopping_rounds: int | None = None, evals_result: dict | None = None) -> Booster:
     """Train on a chunk stream with host-resident pages (one page per chunk) and a per-tree MVS sample
     of about ``sample_rate * n_rows`` rows on the device. Pages up to ``device_page_bytes`` in total
-    stay in HBM (no PCIe traffic per tree); the rest are spilled to pinned host memory."""
+    stay in HBM (no PCIe traffic per tree); the rest are spilled to pinned host memory.
+    Validation sets and early stopping (``gbdt.train``'s ``evals`` ...) are not supported here."""
+    if evals or early_stopping_rounds is not None or evals_result is not None:
+        raise ValueError("train_external does not support evals / early_stopping_rounds: score the model "
+                         "afterwards with Booster.eval_curve, or fit in core with gbdt.train")
     if params is None:
         params = GBDTParams()
     elif isinstance(params, dict):

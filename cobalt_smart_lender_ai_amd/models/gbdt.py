@@ -384,12 +384,109 @@ def check_gpu_shape(max_depth: int, n_rows: int) -> None:
                          "(data parallel) or stream them (models.external.train_external)")
 
 
+class EvalMonitor:
+    """The validation sets of one fit: their per-round metric curves and XGBoost's early-stopping rule.
+
+    ``evals`` = ``[(X_val, y_val[, w_val]), ...]`` (raw float32 features; never binned). The trainer hands
+    over the new trees segment by segment (:meth:`add_trees`); every set's margins are carried forward,
+    so each tree is walked once per validation row (``Booster.eval_curve``). The LAST set and the LAST
+    metric drive early stopping: the best round moves on a strict improvement ("logloss" / "error"
+    minimised, "auc" maximised) and the fit stops at the first round ``r`` with ``r - best >=
+    early_stopping_rounds``. ``scale_pos_weight`` does not enter the metrics."""
+
+    def __init__(self, evals, eval_metric=None, early_stopping_rounds: int | None = None, device=None,
+                 n_features: int | None = None, verbose: bool = False):
+        from .booster import check_eval_inputs
+
+        if early_stopping_rounds is not None and int(early_stopping_rounds) < 1:
+            raise ValueError("early_stopping_rounds must be >= 1")
+        self.rounds = int(early_stopping_rounds) if early_stopping_rounds is not None else None
+        if eval_metric is None:
+            eval_metric = ["logloss"]
+        self.metrics = [eval_metric] if isinstance(eval_metric, str) else list(eval_metric)
+        if not self.metrics:
+            raise ValueError("eval_metric is empty")
+        self.dev = torch.device(device) if device is not None else torch.device("cpu")
+        self.verbose = bool(verbose)
+        self.sets = []
+        for i, ev in enumerate(evals):
+            if not isinstance(ev, (tuple, list)) or len(ev) not in (2, 3):
+                raise ValueError(f"evals[{i}] must be (X, y) or (X, y, sample_weight)")
+            Xv = _to_tensor(ev[0], self.dev)
+            if Xv.ndim != 2 or (n_features is not None and Xv.shape[1] != n_features):
+                raise ValueError(f"evals[{i}]: X has shape {tuple(Xv.shape)}, the training data has "
+                                 f"{n_features} features")
+            yv = _to_tensor(ev[1], "cpu").reshape(-1).numpy()
+            wv = _to_tensor(ev[2], "cpu").reshape(-1).numpy() if len(ev) == 3 and ev[2] is not None else None
+            check_eval_inputs(int(Xv.shape[0]), yv, wv, self.metrics)
+            self.sets.append((Xv if self.dev.type == "cuda" else Xv.numpy(), yv, wv))
+        self.margins: list = [None] * len(self.sets)
+        self.curves = [{m: [] for m in self.metrics} for _ in self.sets]
+        self.best: int | None = None
+        self.best_score: float | None = None
+        self.stopped: int | None = None   # global index of the round at which the rule fired
+
+    def start_from(self, init_booster: Booster) -> None:
+        """The sets' margins under the model that boosting continues from (one pass over its trees)."""
+        self.margins = [init_booster.predict_margin(Xv, device=self.dev) for Xv, _, _ in self.sets]
+
+    def add_trees(self, segment: Booster, first_round: int) -> int | None:
+        """Score the trees of ``segment`` (global rounds ``first_round ...``) on every set and apply the
+        rule round by round; returns the round at which the fit stops (it keeps trees 0..that round)."""
+        from .booster import EVAL_MAXIMIZE
+
+        got = []
+        for i, (Xv, yv, wv) in enumerate(self.sets):
+            curve, self.margins[i] = segment.eval_curve(Xv, yv, wv, self.metrics, device=self.dev,
+                                                        margin=self.margins[i])
+            got.append(curve)
+        keep = segment.num_trees
+        if self.rounds is not None:
+            drive, bigger = got[-1][self.metrics[-1]], EVAL_MAXIMIZE[self.metrics[-1]]
+            for j in range(segment.num_trees):
+                r, s = first_round + j, float(drive[j])
+                if self.best is None or (s > self.best_score if bigger else s < self.best_score):
+                    self.best, self.best_score = r, s
+                elif r - self.best >= self.rounds:
+                    self.stopped, keep = r, j + 1
+                    break
+        for i, curve in enumerate(got):
+            for m in self.metrics:
+                self.curves[i][m].extend(float(v) for v in curve[m][:keep])
+            if self.verbose:
+                for j in range(keep):
+                    print(f"[{first_round + j}]\t" + "\t".join(
+                        f"validation_{k}-{m}:{got[k][m][j]:.5f}" for k in range(len(got)) for m in self.metrics))
+        return self.stopped
+
+    def result(self) -> dict[str, dict[str, list[float]]]:
+        return {f"validation_{i}": {m: list(v) for m, v in c.items()} for i, c in enumerate(self.curves)}
+
+
+def _eval_monitor(evals, eval_metric, early_stopping_rounds, dev, n_features, dist, checkpointing: bool,
+                  verbose: bool = False) -> EvalMonitor | None:
+    """The fit's :class:`EvalMonitor` (None without ``evals``); everything unsupported is refused here,
+    before any device work or collective."""
+    if isinstance(evals, EvalMonitor):
+        return evals
+    if not evals:
+        if early_stopping_rounds is not None:
+            raise ValueError("early_stopping_rounds needs at least one validation set (evals / eval_set)")
+        return None
+    if dist is not None and dist.world > 1:
+        raise ValueError("evals are not supported in data-parallel fits (dist.world > 1)")
+    if early_stopping_rounds is not None and checkpointing:
+        raise ValueError("early_stopping_rounds cannot be combined with checkpoint_path")
+    return EvalMonitor(evals, eval_metric, early_stopping_rounds, dev, n_features, verbose)
+
+
 def train(X, y, params: GBDTParams | dict | None = None, *, sample_weight=None, device=None,
           feature_names: Sequence[str] | None = None, feature_types: Sequence[str] | None = None,
           dist=None, n_rows_global: int | None = None, row_offset: int = 0,
           report: FitReport | None = None, init_booster: Booster | None = None,
           checkpoint_path: str | None = None, checkpoint_every: int = 0, resume: bool = True,
-          exact_fp64: bool = False) -> Booster:
+          exact_fp64: bool = False, evals=None, eval_metric=None, early_stopping_rounds: int | None = None,
+          evals_result: dict | None = None, es_segment: int | None = None, verbose_eval: bool = False) -> Booster:
     """Fit a binary:logistic GBDT. With ``dist`` (a :class:`~..parallel.dist.DistContext`) each rank
     passes its local row shard (``row_offset`` = global index of its first row).
 
@@ -400,12 +497,24 @@ def train(X, y, params: GBDTParams | dict | None = None, *, sample_weight=None, 
     because sampling is keyed by the global tree index and the margins are re-predicted in tree order.
 
     ``exact_fp64`` (CPU only): unquantised fp64 gradients and histograms -- the accuracy reference of
-    the fixed-point trainer (tests/test_quantization.py)."""
+    the fixed-point trainer (tests/test_quantization.py).
+
+    ``evals`` = ``[(X_val, y_val[, w_val]), ...]`` + ``eval_metric`` ("logloss" (default), "error", "auc", or
+    a list) record the metrics after every new round into ``evals_result`` (``{"validation_0": {metric:
+    [...]}, ...}``); ``early_stopping_rounds`` stops the fit by XGBoost's rule on the last set's last metric
+    (:class:`EvalMonitor`) and stores ``best_iteration`` / ``best_score`` in the model's attributes. The
+    early-stopped model is a byte-identical prefix of the full fit; a fit without ``evals`` is untouched.
+    ``es_segment``: trees grown between two looks at the curve (default ``early_stopping_rounds``: the rule
+    cannot fire sooner than that many rounds after the best one, so at most that many trees minus one are
+    grown in vain); it does not change the result. Not supported (``ValueError``): data-parallel fits,
+    ``early_stopping_rounds`` with ``checkpoint_path``."""
     if params is None:
         params = GBDTParams()
     elif isinstance(params, dict):
         params = GBDTParams.from_kwargs(**params)
     t0 = time.perf_counter()
+    evals = _eval_monitor(evals, eval_metric, early_stopping_rounds, _resolve_device(device, X), int(X.shape[1]),
+                          dist, checkpoint_path is not None, verbose_eval)
     ckpt = Checkpointer(checkpoint_path, checkpoint_every, params, dist) if checkpoint_path else None
     total = None
     if ckpt is not None and resume and init_booster is None:
@@ -434,7 +543,8 @@ def train(X, y, params: GBDTParams | dict | None = None, *, sample_weight=None, 
                      sketch_mode=params.sketch_mode)
     bst = train_binned(bd, y, params, sample_weight=sample_weight, feature_names=feature_names,
                        feature_types=feature_types, dist=dist, report=report, init_booster=init_booster,
-                       init_margin=init_margin, total_trees=total, checkpoint=ckpt, exact_fp64=exact_fp64)
+                       init_margin=init_margin, total_trees=total, checkpoint=ckpt, exact_fp64=exact_fp64,
+                       evals=evals, evals_result=evals_result, es_segment=es_segment)
     if report is not None:
         report.t_total = time.perf_counter() - t0
     return bst
@@ -445,17 +555,25 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
                  feature_mask: np.ndarray | None = None, dist=None, report: FitReport | None = None,
                  init_booster: Booster | None = None, init_margin: torch.Tensor | None = None,
                  total_trees: int | None = None, checkpoint: "Checkpointer | None" = None,
-                 exact_fp64: bool = False) -> Booster:
+                 exact_fp64: bool = False, evals=None, eval_metric=None, early_stopping_rounds: int | None = None,
+                 evals_result: dict | None = None, es_segment: int | None = None) -> Booster:
     """Boost on pre-binned data. ``feature_mask`` (bool [F]) restricts the fit to a feature subset
     (the trees still index the full feature space, so a subset fit costs no re-binning).
     ``init_booster`` + ``init_margin`` (its margins on these rows) continue an existing model: grow
-    ``total_trees - init_booster.num_trees`` trees (default ``n_estimators`` more)."""
+    ``total_trees - init_booster.num_trees`` trees (default ``n_estimators`` more).
+    ``evals`` / ``eval_metric`` / ``early_stopping_rounds`` / ``evals_result`` / ``es_segment``: see
+    :func:`train` (with ``init_booster`` the curves cover the new rounds; ``best_iteration`` is a global
+    tree index)."""
     if params is None:
         params = GBDTParams()
     elif isinstance(params, dict):
         params = GBDTParams.from_kwargs(**params)
     dev = bd.device
     world = dist.world if dist is not None else 1
+    mon = _eval_monitor(evals, eval_metric, early_stopping_rounds, dev, bd.n_features, dist, checkpoint is not None)
+    early = mon is not None and mon.rounds is not None
+    if es_segment is not None and int(es_segment) < 1:
+        raise ValueError("es_segment must be >= 1")
     grad_bits = int(params.grad_bits)
     N, F = bd.n_rows, bd.n_features
     check_grad_bits(grad_bits, F, dev.type)
@@ -475,6 +593,8 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
     T0 = init_booster.num_trees if init_booster is not None else 0
     if init_booster is not None and init_margin is None:
         raise ValueError("init_booster needs init_margin (its margins on the training rows)")
+    if mon is not None and T0:
+        mon.start_from(init_booster)
     # base score = weighted label mean (XGBoost boost_from_average for binary:logistic) and the largest
     # weight (the fixed-point scales); under data parallelism both in ONE collective: [sum w, sum w y,
     # every rank's max weight in its own slot] summed on the device
@@ -523,6 +643,8 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
         sub = feature_masks(T, len(active), float(params.colsample_bytree), int(params.random_state))
         fmask_np[:, active] = sub
     seg = checkpoint.every if checkpoint is not None and checkpoint.every > 0 else max(T_new, 1)
+    if early:  # grow a segment, look at the validation curve, stop or go on
+        seg = int(es_segment) if es_segment is not None else mon.rounds
     trees_so_far = list(init_booster.trees) if init_booster is not None else []
     names = list(feature_names) if feature_names is not None else (
         list(init_booster.feature_names) if init_booster is not None and init_booster.feature_names else None)
@@ -537,6 +659,15 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
                                          reg_alpha=hp.reg_alpha, subsample=hp.subsample,
                                          colsample_bytree=float(params.colsample_bytree),
                                          max_bin=int(params.max_bin), scale_pos_weight=spw, seed=hp.seed))
+
+    def early_stop(s0: int) -> bool:
+        """Early stopping: score the segment's trees (rounds s0 ...); on a stop keep trees 0..that round."""
+        if not early:
+            return False
+        stop = mon.add_trees(make_booster(trees_so_far[s0:]), s0)
+        if stop is not None:
+            del trees_so_far[stop + 1:]
+        return stop is not None
 
     def segment_done(new_nodes: np.ndarray, end: int) -> None:
         trees_so_far.extend(trees_from_heap_nodes(new_nodes, hp.max_depth))
@@ -597,7 +728,7 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
                 if cr == dist.rank:
                     tr.set_fault(int(knob("COBALT_FAULT_CORRUPT_TREE", "1") or 1))
             head = None
-            if checkpoint is None and T - T0 >= 64 and _own_device(world):
+            if checkpoint is None and not early and T - T0 >= 64 and _own_device(world):
                 # Two grow calls: the first part's trees are fetched (on a side stream) and converted on
                 # the host while the GPU grows the last ones -- the host's ~1 ms per 300 trees of
                 # fetch + conversion leaves the fit's critical path.
@@ -628,6 +759,8 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
                 tp = rep.mark("fetch", tp, dev)
                 segment_done(seg_nodes, s1)
                 tp = rep.mark("convert", tp, dev)
+                if early_stop(s0):  # (every grown tree was fetched: the context can be parked)
+                    break
             completed = True
         finally:
             tr.close(park=completed)  # a completed fit's context is kept for the next fit of these shapes
@@ -654,12 +787,24 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
                 recs.append(gbdt_host.grow_tree_host(bd.bins_host, cuts_np, nb_np, gq, hq, margin_np, hp,
                                                      fmask_np[t], allreduce))
             segment_done(np.stack(recs), s1)
+            if early_stop(s0):
+                break
         rep.extra["margin"] = margin_np
     t_boost = time.perf_counter() - tb
     tp = rep.mark("to_trees", tp, dev)
     bst = make_booster(trees_so_far)
+    if mon is not None:
+        if not early and len(trees_so_far) > T0:  # the whole curve of the new trees in one pass per set
+            mon.add_trees(make_booster(trees_so_far[T0:]), T0)
+        if early and mon.best is not None:
+            bst.attributes["best_iteration"] = str(mon.best)
+            bst.attributes["best_score"] = repr(mon.best_score)
+        if evals_result is not None:
+            evals_result.clear()
+            evals_result.update(mon.result())
     if report is not None:
-        report.n_rows, report.n_rows_global, report.n_features, report.n_trees = N, bd.n_rows_global, F, T
+        report.n_rows, report.n_rows_global, report.n_features = N, bd.n_rows_global, F
+        report.n_trees = len(trees_so_far)
         report.device, report.world = str(dev), world
         report.t_sketch, report.t_bin, report.t_boost = bd.t_sketch, bd.t_bin, t_boost
         report.extra["cuts"] = bd.cuts
@@ -786,13 +931,13 @@ class GBDTClassifier:
     _param_names = ["n_estimators", "max_depth", "learning_rate", "gamma", "min_child_weight", "reg_lambda",
                     "reg_alpha", "subsample", "colsample_bytree", "max_bin", "scale_pos_weight", "random_state",
                     "base_score", "eval_metric", "use_label_encoder", "device", "importance_type", "n_jobs",
-                    "sketch_rows", "sketch_weight"]
+                    "sketch_rows", "sketch_weight", "early_stopping_rounds"]
 
     def __init__(self, n_estimators=None, max_depth=None, learning_rate=None, gamma=None, min_child_weight=None,
                  reg_lambda=None, reg_alpha=None, subsample=None, colsample_bytree=None, max_bin=None,
                  scale_pos_weight=None, random_state=None, base_score=None, eval_metric=None,
                  use_label_encoder=None, device=None, importance_type=None, n_jobs=None, sketch_rows=None,
-                 sketch_weight=None):
+                 sketch_weight=None, early_stopping_rounds=None):
         self.n_estimators = n_estimators
         self.max_depth = max_depth
         self.learning_rate = learning_rate
@@ -813,6 +958,7 @@ class GBDTClassifier:
         self.n_jobs = n_jobs
         self.sketch_rows = sketch_rows
         self.sketch_weight = sketch_weight
+        self.early_stopping_rounds = early_stopping_rounds
 
     # sklearn protocol
     def get_params(self, deep: bool = True) -> dict[str, Any]:
@@ -836,9 +982,15 @@ class GBDTClassifier:
         kw = {k: v for k, v in self.get_params().items() if v is not None}
         return GBDTParams.from_kwargs(**{k: v for k, v in {**XGB_DEFAULTS, **kw}.items()})
 
-    def fit(self, X, y, sample_weight=None, xgb_model=None, **_):
+    def fit(self, X, y, sample_weight=None, xgb_model=None, eval_set=None, sample_weight_eval_set=None,
+            verbose=None, **_):
         """``xgb_model`` (a Booster, a fitted classifier or a model/pickle path) continues boosting
-        from that model for ``n_estimators`` more trees, as XGBoost's ``fit(xgb_model=...)``."""
+        from that model for ``n_estimators`` more trees, as XGBoost's ``fit(xgb_model=...)``.
+
+        ``eval_set`` = ``[(X_val, y_val), ...]`` (+ ``sample_weight_eval_set``, one weight vector or None
+        per set): the constructor's ``eval_metric`` (default "logloss") is recorded after every round
+        (:meth:`evals_result`), and with ``early_stopping_rounds`` the fit stops by XGBoost's rule on
+        the last set's last metric (:func:`train`); ``verbose`` prints the rounds."""
         names, types = _feature_info(X)
         init = None
         if xgb_model is not None:
@@ -862,9 +1014,29 @@ class GBDTClassifier:
             raise ValueError("GBDTClassifier supports binary targets")
         self.n_classes_ = 2
         yb = (y_np == self.classes_[-1]).astype(np.float32) if len(self.classes_) == 2 else y_np.astype(np.float32)
+        evals = None
+        if eval_set:
+            wts = list(sample_weight_eval_set) if sample_weight_eval_set is not None else [None] * len(eval_set)
+            if len(wts) != len(eval_set):
+                raise ValueError("sample_weight_eval_set needs one entry per eval_set entry")
+            evals = []
+            for (Xv, yv), wv in zip(eval_set, wts):
+                yv = np.asarray(yv.to_numpy() if hasattr(yv, "to_numpy") else yv).reshape(-1)
+                if not np.isin(yv, self.classes_).all():
+                    raise ValueError("eval_set labels must be among the training classes")
+                yvb = (yv == self.classes_[-1]).astype(np.float32) if len(self.classes_) == 2 else yv.astype(np.float32)
+                evals.append((self._matrix_named(Xv, names), yvb, wv))
         rep = FitReport()
+        history: dict = {}
         self._Booster = train(X, yb, self._train_params(), sample_weight=sample_weight, device=self.device,
-                              feature_names=names, feature_types=types, report=rep, init_booster=init)
+                              feature_names=names, feature_types=types, report=rep, init_booster=init,
+                              evals=evals, eval_metric=self.eval_metric,
+                              early_stopping_rounds=self.early_stopping_rounds, evals_result=history,
+                              verbose_eval=bool(verbose))
+        if evals is not None:
+            self.evals_result_ = history
+        elif hasattr(self, "evals_result_"):
+            del self.evals_result_
         self.fit_report_ = rep
         self.n_features_in_ = self._Booster.num_feature
         if names is not None:
@@ -876,21 +1048,60 @@ class GBDTClassifier:
             raise ValueError("need to call fit or load_model beforehand")
         return self._Booster
 
-    def _matrix(self, X) -> np.ndarray | torch.Tensor:
+    @staticmethod
+    def _matrix_named(X, names) -> np.ndarray | torch.Tensor:
         if isinstance(X, torch.Tensor):
             return X
-        if hasattr(X, "columns") and getattr(self, "feature_names_in_", None) is not None:
-            X = X[list(self.feature_names_in_)]
+        if hasattr(X, "columns") and names is not None:
+            X = X[list(names)]
         return np.asarray(X.to_numpy(dtype=np.float32, na_value=np.nan) if hasattr(X, "to_numpy") else X,
                           dtype=np.float32)
 
-    def predict_proba(self, X) -> np.ndarray:
-        p = self.get_booster().predict_proba(self._matrix(X), device=self.device)
+    def _matrix(self, X) -> np.ndarray | torch.Tensor:
+        return self._matrix_named(X, getattr(self, "feature_names_in_", None))
+
+    def evals_result(self) -> dict[str, dict[str, list[float]]]:
+        """``{"validation_0": {metric: [value per round]}, ...}`` of the last ``fit(eval_set=...)``."""
+        if not hasattr(self, "evals_result_"):
+            raise ValueError("no evaluation results: call fit with eval_set")
+        return self.evals_result_
+
+    @property
+    def best_iteration(self) -> int:
+        """Best round of an early-stopped fit (a global tree index)."""
+        v = self.get_booster().best_iteration
+        if v is None:
+            raise AttributeError("best_iteration is only defined after a fit with early_stopping_rounds")
+        return v
+
+    @property
+    def best_score(self) -> float:
+        v = self.get_booster().best_score
+        if v is None:
+            raise AttributeError("best_score is only defined after a fit with early_stopping_rounds")
+        return v
+
+    def _n_trees(self, iteration_range) -> int | None:
+        """Trees to score: the prefix ``iteration_range = (0, n)`` (``(0, 0)``: all); by default the first
+        ``best_iteration + 1`` trees of an early-stopped model, else all (None)."""
+        b = self.get_booster()
+        if iteration_range is None:
+            n = b.best_iteration + 1 if b.best_iteration is not None else b.num_trees
+        else:
+            lo, hi = (int(v) for v in iteration_range)
+            if lo != 0 or hi < 0 or hi > b.num_trees:
+                raise ValueError(f"iteration_range must be (0, n) with n <= {b.num_trees} trees, got {iteration_range}")
+            n = hi if hi > 0 else b.num_trees
+        return None if n >= b.num_trees else n
+
+    def predict_proba(self, X, iteration_range=None) -> np.ndarray:
+        p = self.get_booster().predict_proba(self._matrix(X), device=self.device,
+                                             n_trees=self._n_trees(iteration_range))
         p = p.cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)
         return np.stack([1.0 - p, p], axis=1)
 
-    def predict(self, X) -> np.ndarray:
-        p = self.predict_proba(X)[:, 1]
+    def predict(self, X, iteration_range=None) -> np.ndarray:
+        p = self.predict_proba(X, iteration_range)[:, 1]
         pred = (p > 0.5).astype(np.int64)
         return self.classes_[pred] if getattr(self, "classes_", None) is not None and len(self.classes_) == 2 else pred
 
@@ -908,7 +1119,7 @@ class GBDTClassifier:
         p = {k: getattr(self, k) for k in ["n_estimators", "max_depth", "learning_rate", "gamma", "min_child_weight",
                                            "reg_alpha", "reg_lambda", "subsample", "colsample_bytree",
                                            "scale_pos_weight", "base_score", "random_state", "max_bin", "device",
-                                           "importance_type", "n_jobs", "eval_metric"]}
+                                           "importance_type", "n_jobs", "eval_metric", "early_stopping_rounds"]}
         p["kwargs"] = {"use_label_encoder": self.use_label_encoder} if self.use_label_encoder is not None else {}
         return p
 

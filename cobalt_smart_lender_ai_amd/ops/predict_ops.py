@@ -1,6 +1,8 @@
-"""Inference entry points: margins, probabilities and TreeSHAP for a :class:`Booster`.
+"""Inference entry points: margins, probabilities, TreeSHAP and per-tree learning curves for a
+:class:`Booster`.
 
-GPU path: gfx950 kernels in ``csrc/predict.hip`` (forest packed once per booster and device, cached).
+GPU path: gfx950 kernels in ``csrc/predict.hip`` (forest packed once per booster and device, cached),
+``csrc/shapint.hip`` and ``csrc/evalcurve.hip``.
 CPU path: the NumPy reference implementations in ``models/booster.py``.
 """
 from __future__ import annotations
@@ -13,8 +15,8 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..models.booster import (Booster, Tree, predict_margin_host, sigmoid32, treeshap_host,
-                              treeshap_interactions_host)
+from ..models.booster import (Booster, Tree, check_eval_inputs, eval_curve_host, predict_margin_host, sigmoid32,
+                              staged_margins_host, treeshap_host, treeshap_interactions_host)
 from ..config import knob
 
 # LDS tile capacity in nodes: a model's tile is max(this, its largest tree), at most MAX_TILE_NODES
@@ -63,6 +65,15 @@ SHAP_INT_MAX_F = 48            # widest model of the interaction kernel (csrc/sh
 # shipped model); the interaction kernel itself keeps its accumulators in LDS and has no global scratch.
 SHAP_INT_ROWS = 16384
 
+# csrc/evalcurve.hip: (X, n, F, ldx, y, w, nodes, tree_ptr, tile_ptr, n_tiles, tile_cap, n_trees, base_margin,
+# margin_in, margin_out, stage_margins, workspace, sums, stream)
+_native.register("cobalt_eval_curve", ctypes.c_int,
+                 [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                  ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p])
+_native.register("cobalt_eval_curve_workspace", ctypes.c_int64, [ctypes.c_int64, ctypes.c_int])
+
 PATH_ELEM = np.dtype([("lo", "<f4"), ("hi", "<f4"), ("feat", "<i4"), ("nan_ok", "<i4"), ("zero", "<f8")])
 
 
@@ -88,6 +99,28 @@ def tile_capacity(b: Booster, n_trees: int | None = None) -> int:
     return cap
 
 
+def _pack_tree(t: Tree) -> tuple[np.ndarray, np.ndarray]:
+    """(meta uint32 [n], val float32 [n]) of one tree in BFS order (csrc/forest_walk.h)."""
+    order = _bfs_order(t)
+    if len(order) > 0xFFFE:
+        raise ValueError("tree too large for the packed predictor")
+    nid = {j: i for i, j in enumerate(order)}
+    meta = np.zeros(len(order), dtype=np.uint32)
+    val = np.zeros(len(order), dtype=np.float32)
+    for j, i in nid.items():
+        if t.left_children[j] == -1:
+            meta[i] = 0xFFFF
+        else:
+            l, r = nid[int(t.left_children[j])], nid[int(t.right_children[j])]
+            assert r == l + 1
+            f = int(t.split_indices[j])
+            if f > 0x7FFF:
+                raise ValueError("feature index too large for the packed predictor")
+            meta[i] = (l & 0xFFFF) | (f << 16) | (int(t.default_left[j]) << 31)
+        val[i] = t.split_conditions[j]
+    return meta, val
+
+
 def pack_forest(b: Booster, n_trees: int | None = None,
                 tile_nodes: int | None = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     """(nodes uint32 [M, 2], tree_ptr int32 [T+1], tile_ptr int32 [n_tiles+1]); trees are grouped into
@@ -95,27 +128,16 @@ def pack_forest(b: Booster, n_trees: int | None = None,
     tile_nodes = tile_capacity(b, n_trees) if tile_nodes is None else tile_nodes
     trees = b.trees[: (n_trees if n_trees is not None else b.num_trees)]
     metas, vals, tree_ptr = [], [], [0]
+    # a tree's packed nodes do not depend on its neighbours: kept per tree, so that packing the prefixes
+    # of one model (predict_margin(n_trees=t) for many t) packs every tree once
+    packed = b.__dict__.setdefault("_packed_trees", {})
     for t in trees:
-        order = _bfs_order(t)
-        if len(order) > 0xFFFE:
-            raise ValueError("tree too large for the packed predictor")
-        nid = {j: i for i, j in enumerate(order)}
-        meta = np.zeros(len(order), dtype=np.uint32)
-        val = np.zeros(len(order), dtype=np.float32)
-        for j, i in nid.items():
-            if t.left_children[j] == -1:
-                meta[i] = 0xFFFF
-            else:
-                l, r = nid[int(t.left_children[j])], nid[int(t.right_children[j])]
-                assert r == l + 1
-                f = int(t.split_indices[j])
-                if f > 0x7FFF:
-                    raise ValueError("feature index too large for the packed predictor")
-                meta[i] = (l & 0xFFFF) | (f << 16) | (int(t.default_left[j]) << 31)
-            val[i] = t.split_conditions[j]
-        metas.append(meta)
-        vals.append(val)
-        tree_ptr.append(tree_ptr[-1] + len(order))
+        ent = packed.get(id(t))
+        if ent is None or ent[0] is not t:
+            ent = packed[id(t)] = (t, *_pack_tree(t))
+        metas.append(ent[1])
+        vals.append(ent[2])
+        tree_ptr.append(tree_ptr[-1] + len(ent[1]))
     M = tree_ptr[-1]
     nodes = np.zeros((M, 2), dtype=np.uint32)
     if M:
@@ -306,14 +328,120 @@ def predict_margin(b: Booster, X, device=None, n_trees: int | None = None):
     return predict_margin_host(b, Xn, n_trees)
 
 
-def predict_proba(b: Booster, X, device=None):
+def predict_proba(b: Booster, X, device=None, n_trees: int | None = None):
     d = _device_of(X, device)
     if d.type == "cuda":
         Xt = _as_f32(X, d)
         out = torch.empty(Xt.shape[0], dtype=torch.float32, device=d)
-        predict_gpu(b, Xt, None, out_prob=out)
+        predict_gpu(b, Xt, n_trees, out_prob=out)
         return out if isinstance(X, torch.Tensor) else out.cpu().numpy()
-    return sigmoid32(predict_margin(b, X, "cpu"))
+    return sigmoid32(predict_margin(b, X, "cpu", n_trees=n_trees))
+
+
+# ------------------------------------------------------------------------------- learning curves
+# Stage margins held at once by the AUC curve (the forest is scored in tree chunks of this many bytes)
+AUC_STAGE_BYTES = 256 << 20
+
+
+def _eval_curve_launch(b: Booster, Xt: torch.Tensor, yt: torch.Tensor | None, wt: torch.Tensor | None,
+                       margin_in: torch.Tensor | None, margin_out: torch.Tensor | None,
+                       stages: torch.Tensor | None) -> torch.Tensor | None:
+    """One ``cobalt_eval_curve`` call over all trees of ``b`` on the current stream; returns the [T, 3]
+    float64 sums (sum w loss, sum w err, sum w) when ``yt`` is given."""
+    gf = gpu_forest(b, Xt.device)
+    N, F = Xt.shape
+    if F < b.num_feature:
+        raise ValueError(f"X has {F} features, model needs {b.num_feature}")
+    lib = _native.lib()
+    sums = work = None
+    if yt is not None:
+        sums = torch.empty((gf.n_trees, 3), dtype=torch.float64, device=Xt.device)
+        work = torch.empty(int(lib.cobalt_eval_curve_workspace(N, gf.n_trees)), dtype=torch.uint8, device=Xt.device)
+    rc = lib.cobalt_eval_curve(Xt.data_ptr(), N, F, Xt.stride(0), _native.ptr(yt), _native.ptr(wt),
+                               gf.nodes.data_ptr(), gf.tree_ptr.data_ptr(), gf.tile_ptr.data_ptr(), gf.n_tiles,
+                               gf.tile_cap, gf.n_trees, b.base_margin, _native.ptr(margin_in),
+                               _native.ptr(margin_out), _native.ptr(stages), _native.ptr(work), _native.ptr(sums),
+                               _native.stream_handle())
+    _native.check(rc, "cobalt_eval_curve")
+    return sums
+
+
+def _tree_range(b: Booster, t0: int, t1: int) -> Booster:
+    return Booster(b.trees[t0:t1], b.feature_names, b.feature_types, b.base_score, b.num_feature, b.objective)
+
+
+def _host_vec(v, dtype=np.float32) -> np.ndarray:
+    return (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(dtype).reshape(-1)
+
+
+def eval_curve(b: Booster, X, y, sample_weight=None, metrics=("logloss",), device=None, margin=None):
+    """``({metric: float64 [num_trees]}, final margins [N] float32)``: the metrics of ``(X, y)`` after every
+    tree. GPU: one pass of ``csrc/evalcurve.hip`` over the forest for "logloss" / "error" (deterministic:
+    the same input gives the same bits); "auc" scores :func:`staged_margins` in bounded tree chunks with
+    :func:`~..metrics.auc.roc_auc` (unweighted). CPU: :func:`~..models.booster.eval_curve_host`.
+    ``margin``: start from these margins instead of the base margin. Raises ``ValueError`` before any
+    launch for labels outside [0, 1], weights that sum to <= 0, row-count mismatches, an unknown metric and
+    "auc" with one class."""
+    d = _device_of(X, device)
+    if d.type != "cuda":
+        Xn = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
+        return eval_curve_host(b, Xn, _host_vec(y), None if sample_weight is None else _host_vec(sample_weight),
+                               metrics, None if margin is None else _host_vec(margin))
+    Xt = _as_f32(X, d)
+    N = Xt.shape[0]
+    # labels and weights are a few bytes per row: they are checked on the host
+    y32 = _host_vec(y)
+    w32 = None if sample_weight is None else _host_vec(sample_weight)
+    m_rows = None if margin is None else int(torch.as_tensor(margin).reshape(-1).shape[0])
+    metrics = check_eval_inputs(N, y32, w32, metrics, m_rows)
+    yt = torch.as_tensor(y32, device=d)
+    wt = None if w32 is None else torch.as_tensor(w32, device=d)
+    m_in = None if margin is None else torch.as_tensor(margin).to(device=d, dtype=torch.float32).reshape(-1).contiguous()
+    T = b.num_trees
+    out: dict[str, np.ndarray] = {}
+    m_out = torch.empty(N, dtype=torch.float32, device=d)
+    if T == 0:
+        m_out = m_in.clone() if m_in is not None else torch.full((N,), b.base_margin, dtype=torch.float32, device=d)
+        out = {m: np.empty(0, dtype=np.float64) for m in metrics}
+    elif "logloss" in metrics or "error" in metrics:
+        s = _eval_curve_launch(b, Xt, yt, wt, m_in, m_out, None).cpu().numpy()
+        if "logloss" in metrics:
+            out["logloss"] = s[:, 0] / s[:, 2]
+        if "error" in metrics:
+            out["error"] = s[:, 1] / s[:, 2]
+    if "auc" in metrics and T:
+        from ..metrics.auc import roc_auc
+
+        auc = np.empty(T, dtype=np.float64)
+        ypos = (yt > 0.5).to(torch.float64)
+        per = max(1, AUC_STAGE_BYTES // max(4 * N, 1))
+        cur = m_in
+        for t0 in range(0, T, per):
+            t1 = min(T, t0 + per)
+            stages = torch.empty((t1 - t0, N), dtype=torch.float32, device=d)
+            nxt = torch.empty(N, dtype=torch.float32, device=d)
+            _eval_curve_launch(b if (t0, t1) == (0, T) else _tree_range(b, t0, t1), Xt, None, None, cur, nxt, stages)
+            for t in range(t0, t1):
+                auc[t] = roc_auc(ypos, stages[t - t0])
+            cur = nxt
+        m_out = cur
+        out["auc"] = auc
+    out = {m: out[m] for m in metrics}
+    return out, (m_out if isinstance(X, torch.Tensor) else m_out.cpu().numpy())
+
+
+def staged_margins(b: Booster, X, device=None):
+    """Margins after every tree, [num_trees, N] float32 (stage ``t`` has the bits of
+    ``predict_margin(n_trees=t + 1)``); one forest pass on the GPU."""
+    d = _device_of(X, device)
+    if d.type != "cuda":
+        Xn = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
+        return staged_margins_host(b, Xn)
+    Xt = _as_f32(X, d)
+    stages = torch.empty((b.num_trees, Xt.shape[0]), dtype=torch.float32, device=d)
+    if b.num_trees and Xt.shape[0]:
+        _eval_curve_launch(b, Xt, None, None, None, None, stages)
+    return stages if isinstance(X, torch.Tensor) else stages.cpu().numpy()
 
 
 def shap_values(b: Booster, X, device=None):
