@@ -31,6 +31,7 @@
 #include <stdlib.h>
 #include <vector>
 #include <algorithm>
+#include <type_traits>
 
 using namespace cobalt;
 
@@ -1581,6 +1582,40 @@ __device__ __forceinline__ double calc_weight(double g, double h, double lambda_
   return -t / (h + lambda_);
 }
 
+// Monotone constraints (constrained mode; models/gbdt_host.py _eval_node_mono is the specification).
+// Every node carries fp64 weight bounds [lo, hi] (root: -inf, +inf) in a workspace array of the context
+// ([max_nodes][2], NOT in Node: its 64-byte layout is shared with the IPC decision table, the replica
+// digest and the host's NODE_DTYPE). A child's weight is calc_weight clamped to the node's bounds, a
+// candidate's gain is the gain GIVEN its children's weights, a candidate on a constrained feature
+// whose weights are in the wrong order is rejected, and the children of a split on a constrained feature
+// take the midpoint of the winner's weights as their common bound. The constrained kernels take the
+// constraint vector and the bounds as one more argument; the unconstrained instantiations carry an
+// empty struct instead (same code as without the feature).
+struct MonoDev {
+  const int8_t* c;  // [F] constraint per feature: -1, 0, +1
+  double* bounds;   // [max_nodes][2] (lo, hi); written by eval_finalize for the children of a split
+};
+struct MonoNone {};
+template <bool kMono>
+using MonoArg = typename std::conditional<kMono, MonoDev, MonoNone>::type;
+
+// min(max(w, lo), hi) by compare-and-select: a zero keeps its sign (as the host's _clamp)
+__device__ __forceinline__ double mono_clamp(double w, double lo, double hi) {
+  w = w < lo ? lo : w;
+  return w > hi ? hi : w;
+}
+
+__device__ __forceinline__ double calc_weight_mono(double g, double h, double lambda_, double alpha, double mcw,
+                                                   double lo, double hi) {
+  return mono_clamp(calc_weight(g, h, lambda_, alpha, mcw), lo, hi);
+}
+
+// -(2 t w + (h + lambda) w^2), in the host's operation order (_gain_given_weight)
+__device__ __forceinline__ double gain_given_weight(double g, double h, double w, double lambda_, double alpha) {
+  const double t = alpha == 0.0 ? g : thresh_l1(g, alpha);
+  return -(2.0 * t * w + (h + lambda_) * w * w);
+}
+
 // Latency structure: one round of scalar loads for the node (and its parent's build flag / the root
 // total), then every wave issues ALL loads of its <= 2 features (histogram bins, parent bins for the
 // subtraction, masks, bin counts, cut values) before computing, so a level costs ~2 dependent memory
@@ -1594,14 +1629,29 @@ struct EvalFeat {
 
 // Node decision from its best candidate (split or leaf; children of the last split level become leaves).
 // `nb_known` >= 0: the winning feature's bin count (the compact evaluator has it in LDS), else loaded.
-template <bool kDP>
+// kMono: the node's weight is clamped to its bounds, a split writes its children's bounds (the winner's
+// weights are recomputed from the children's sums: the same fp64 values the candidate was scored with)
+// and the max-depth leaves take the bounds just computed.
+template <bool kDP, bool kMono = false>
 __device__ void eval_finalize(const GbdtDev& d, int level, int n, int64_t G, int64_t H, Cand best, float best_cut,
-                              int nb_known = -1) {
+                              int nb_known = -1, MonoArg<kMono> mono = {}) {
   Node* nodes = d.nodes;
   const double Gd = (double)G * d.ginv, Hd = (double)H * d.hinv;
   const float loss = (float)best.gain;
   const bool ok = best.key != 0x7fffffff && loss > 1e-6f && loss >= (float)d.gamma;
-  const double wgt = calc_weight(Gd, Hd, d.lambda_, d.alpha, d.mcw);
+  double wgt = calc_weight(Gd, Hd, d.lambda_, d.alpha, d.mcw);
+  double blo = -INFINITY, bhi = INFINITY;        // kMono: this node's bounds (the root's are the whole line)
+  double clo[2] = {blo, blo}, chi[2] = {bhi, bhi};  // ... and its children's (L, R)
+  if constexpr (kMono) {
+    if (level == 0) {  // the root's entry is reset with every tree
+      mono.bounds[0] = blo;
+      mono.bounds[1] = bhi;
+    } else {
+      blo = mono.bounds[2 * n];
+      bhi = mono.bounds[2 * n + 1];
+    }
+    wgt = mono_clamp(wgt, blo, bhi);
+  }
   Node& nd = nodes[n];
   if (level == 0) { nd.G = G; nd.H = H; }
   nd.sum_hess = (float)Hd;
@@ -1628,12 +1678,27 @@ __device__ void eval_finalize(const GbdtDev& d, int level, int n, int64_t G, int
     const int lb = best.hl <= H - best.hl ? 1 : 0;
     L.build = lb;
     R.build = 1 - lb;
+    if constexpr (kMono) {
+      const double wl = calc_weight_mono((double)best.gl * d.ginv, (double)best.hl * d.hinv, d.lambda_, d.alpha, d.mcw,
+                                         blo, bhi);
+      const double wr = calc_weight_mono((double)(G - best.gl) * d.ginv, (double)(H - best.hl) * d.hinv, d.lambda_,
+                                         d.alpha, d.mcw, blo, bhi);
+      const double mid = (wl + wr) / 2;
+      const int cf = mono.c[f];
+      clo[0] = cf < 0 ? mid : blo;
+      chi[0] = cf > 0 ? mid : bhi;
+      clo[1] = cf > 0 ? mid : blo;
+      chi[1] = cf < 0 ? mid : bhi;
+      double* cb = mono.bounds + 2 * (2 * n + 1);  // (L, R) adjacent
+      cb[0] = clo[0]; cb[1] = chi[0]; cb[2] = clo[1]; cb[3] = chi[1];
+    }
     if (level + 1 == d.max_depth) {  // children are at max depth: finalise them as leaves here
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         Node& ch = c == 0 ? L : R;
         const double cg = (double)ch.G * d.ginv, chh = (double)ch.H * d.hinv;
-        const double cw = calc_weight(cg, chh, d.lambda_, d.alpha, d.mcw);
+        double cw = calc_weight(cg, chh, d.lambda_, d.alpha, d.mcw);
+        if constexpr (kMono) cw = mono_clamp(cw, clo[c], chi[c]);
         ch.sum_hess = (float)chh;
         ch.base_weight = (float)(cw * d.eta);
         ch.status = kLeaf;
@@ -1898,9 +1963,12 @@ struct EvalOut {
 // node may already have finalised it), and only `store_hist` blocks store its histogram.
 // kDP: data parallel (kFused implies it): the level-0 replica-digest check and the fault-injection hook;
 // the single-GPU instantiation carries neither.
-template <bool kGroups, bool kFused, bool kDP, bool kMerged = false>
+// kMono (one GPU, no exchange): monotone constraints -- candidates are scored by score_mono below.
+template <bool kGroups, bool kFused, bool kDP, bool kMerged = false, bool kMono = false>
 __device__ __forceinline__ bool eval_core(const GbdtDev& d, int level, int parity, int tree, int fg, const EvalSlots& es,
-                                          int pos, BlockStamp& stamp_, EvalOut* s_out, bool store_hist = true) {
+                                          int pos, BlockStamp& stamp_, EvalOut* s_out, bool store_hist = true,
+                                          MonoArg<kMono> mono = {}) {
+  static_assert(!kMono || (!kFused && !kDP && !kMerged), "constrained fits run on one GPU, unfused");
   const int fbeg = kGroups ? blockIdx.y * fg : 0;
   const int fend = kGroups ? min(d.F, fbeg + fg) : d.F;
   const int n = (1 << level) - 1 + pos;
@@ -2060,8 +2128,29 @@ __device__ __forceinline__ bool eval_core(const GbdtDev& d, int level, int parit
   }
   const double Gd = (double)G * d.ginv, Hd = (double)H * d.hinv;
   // wave-uniform: kept in SGPRs (as a VALU result it held a VGPR pair the candidate loop spilled)
-  const double parent_gain = __longlong_as_double(
+  double parent_gain = __longlong_as_double(
       readlane64(__double_as_longlong(calc_gain(Gd, Hd, d.lambda_, d.alpha, d.mcw)), 0));
+  // kMono: the node's bounds (uniform address: scalar loads) and the gain of its bounded weight; like
+  // parent_gain, wave-uniform values pinned to SGPRs
+  double blo = -INFINITY, bhi = INFINITY;
+  if constexpr (kMono) {
+    if (level > 0) {
+      blo = __longlong_as_double(readlane64(__double_as_longlong(mono.bounds[2 * n]), 0));
+      bhi = __longlong_as_double(readlane64(__double_as_longlong(mono.bounds[2 * n + 1]), 0));
+    }
+    const double pw = calc_weight_mono(Gd, Hd, d.lambda_, d.alpha, d.mcw, blo, bhi);
+    const double pgm = Hd < d.mcw ? 0.0 : gain_given_weight(Gd, Hd, pw, d.lambda_, d.alpha);
+    parent_gain = __longlong_as_double(readlane64(__double_as_longlong(pgm), 0));
+  }
+  // a candidate's gain under constraint `cf` of its feature; false: rejected (weights in the wrong order)
+  auto score_mono = [&](double gl, double hl, double gr, double hr, int cf, double& gain) -> bool {
+    const double wl = calc_weight_mono(gl, hl, d.lambda_, d.alpha, d.mcw, blo, bhi);
+    const double wr = calc_weight_mono(gr, hr, d.lambda_, d.alpha, d.mcw, blo, bhi);
+    if ((cf > 0 && wl > wr) || (cf < 0 && wl < wr)) return false;
+    gain = gain_given_weight(gl, hl, wl, d.lambda_, d.alpha) + gain_given_weight(gr, hr, wr, d.lambda_, d.alpha) -
+           parent_gain;
+    return true;
+  };
   Cand best;
   best.gain = -INFINITY;
   best.key = 0x7fffffff;
@@ -2100,6 +2189,8 @@ __device__ __forceinline__ bool eval_core(const GbdtDev& d, int level, int parit
     if (!e.on) continue;
     const int f = e.f, nb = e.nb;
     const int nch = (nb + kWave - 1) / kWave;  // wave-uniform
+    int cf = 0;  // kMono: this feature's constraint (wave-uniform)
+    if constexpr (kMono) cf = __builtin_amdgcn_readfirstlane((int)mono.c[__builtin_amdgcn_readfirstlane(f)]);
     if (active && store_hist && level + 1 < d.max_depth) {  // this node's histogram, for its children's subtraction
       longlong2* hs2 = reinterpret_cast<longlong2*>(hs);
 #pragma unroll
@@ -2151,11 +2242,13 @@ __device__ __forceinline__ bool eval_core(const GbdtDev& d, int level, int parit
           const double gr = (GD - GLd) * d.ginv, hr = (HD - HLd) * d.hinv;
           if (hl >= d.mcw && hr >= d.mcw) {
             Cand cd;
-            cd.gain = calc_gain_pair(gl, hl, gr, hr, d.lambda_, d.alpha) - parent_gain;
+            bool keep = true;
+            if constexpr (kMono) keep = score_mono(gl, hl, gr, hr, cf, cd.gain);
+            else cd.gain = calc_gain_pair(gl, hl, gr, hr, d.lambda_, d.alpha) - parent_gain;
             cd.key = f * 1024 + b;
             cd.gl = GL;
             cd.hl = HL;
-            if (cand_better(cd, best)) { best = cd; best_cut = rcut[0]; }
+            if (keep && cand_better(cd, best)) { best = cd; best_cut = rcut[0]; }
           }
         }
         // direction 1: missing -> left, left = bins <= b-1 (+ missing)
@@ -2166,11 +2259,13 @@ __device__ __forceinline__ bool eval_core(const GbdtDev& d, int level, int parit
           const double gr = (GD - GL1) * d.ginv, hr = (HD - HL1) * d.hinv;
           if (hl >= d.mcw && hr >= d.mcw) {
             Cand cd;
-            cd.gain = calc_gain_pair(gl, hl, gr, hr, d.lambda_, d.alpha) - parent_gain;
+            bool keep = true;
+            if constexpr (kMono) keep = score_mono(gl, hl, gr, hr, cf, cd.gain);
+            else cd.gain = calc_gain_pair(gl, hl, gr, hr, d.lambda_, d.alpha) - parent_gain;
             cd.key = f * 1024 + 512 + (nb - 1 - b);
             cd.gl = GL;
             cd.hl = HL;
-            if (cand_better(cd, best)) { best = cd; best_cut = b == 0 ? -FLT_MAX : cutp; }
+            if (keep && cand_better(cd, best)) { best = cd; best_cut = b == 0 ? -FLT_MAX : cutp; }
           }
         }
       }
@@ -2248,10 +2343,35 @@ __global__ __launch_bounds__(1024) void k_eval(GbdtDev d, int level, int parity,
   stamp_.probe(4);
 }
 
-// Reduce the per-group candidates of each node of the level (one wave per node, lane = group).
-template <bool kDP>
-__global__ __launch_bounds__(64) void k_eval_finish(GbdtDev d, int level, int parity, int ngroups) {
+// k_eval<kGroups, false, false> under monotone constraints (one GPU): the constraint vector and the nodes'
+// bounds are one more argument, so the unconstrained kernels keep their argument list.
+template <bool kGroups>
+__global__ __launch_bounds__(1024) void k_eval_mono(GbdtDev d, int level, int parity, int tree, int fg, EvalSlots es,
+                                                    MonoDev mono) {
   BlockStamp stamp_(d);
+  const int pos = blockIdx.x;
+  __shared__ EvalOut s_out;
+  if (!eval_core<kGroups, false, false, false, true>(d, level, parity, tree, fg, es, pos, stamp_, &s_out, true, mono))
+    return;
+  if (threadIdx.x != 0) return;  // thread 0 wrote s_out
+  const Cand best = s_out.best;
+  if (kGroups) {
+    CandRec& o = d.cand[(int64_t)pos * gridDim.y + blockIdx.y];
+    o.gain = best.gain;
+    o.key = best.key;
+    o.cut = s_out.cut;
+    o.gl = best.gl;
+    o.hl = best.hl;
+    return;
+  }
+  eval_finalize<false, true>(d, level, (1 << level) - 1 + pos, s_out.G, s_out.H, best, s_out.cut, s_out.nb, mono);
+  stamp_.probe(4);
+}
+
+// Reduce the per-group candidates of each node of the level (one wave per node, lane = group).
+template <bool kDP, bool kMono = false>
+__device__ __forceinline__ void eval_finish_node(const GbdtDev& d, int level, int parity, int ngroups,
+                                                 MonoArg<kMono> mono = {}) {
   const int pos = blockIdx.x;
   const int n = (1 << level) - 1 + pos;
   const Node& nd = d.nodes[n];
@@ -2277,7 +2397,18 @@ __global__ __launch_bounds__(64) void k_eval_finish(GbdtDev d, int level, int pa
     best_cut = c.cut;
   }
   wave_best(best, best_cut);
-  if (lane == 0) eval_finalize<kDP>(d, level, n, G, H, best, best_cut);
+  if (lane == 0) eval_finalize<kDP, kMono>(d, level, n, G, H, best, best_cut, -1, mono);
+}
+
+template <bool kDP>
+__global__ __launch_bounds__(64) void k_eval_finish(GbdtDev d, int level, int parity, int ngroups) {
+  BlockStamp stamp_(d);
+  eval_finish_node<kDP>(d, level, parity, ngroups);
+}
+
+__global__ __launch_bounds__(64) void k_eval_finish_mono(GbdtDev d, int level, int parity, int ngroups, MonoDev mono) {
+  BlockStamp stamp_(d);
+  eval_finish_node<false, true>(d, level, parity, ngroups, mono);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2936,6 +3067,10 @@ struct GbdtCtx {
   int fault_tree = -1;          // fault injection: tree whose root totals are perturbed on this rank
   uint32_t dec_tag = 0;         // k_eval_part<.., 2>: the launch tag of the decision granules (d.dec)
   bool label_pending = false;   // lab31 labels set, to be written into the records by the next grow call
+  // monotone constraints of the current fit (cobalt_gbdt_set_monotone; cleared by cobalt_gbdt_reuse): the
+  // constraint vector and the nodes' weight bounds, allocated on first use and kept with the context
+  bool mono_on = false;
+  MonoDev mono{};
   // the last grow call's plan (cobalt_gbdt_plan): fused IPC exchange, ownership level, wide gradients,
   // resident blocks of the fused k_eval, levels run by the fused evaluation + partition pass (and of them
   // the evaluator-block levels, and those whose grid exceeds one block per CU)
@@ -3479,7 +3614,11 @@ static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool s
     l0 = std::max(l0, D - 3);
     d.own_level = l0 < D ? l0 : -1;
   }
-  const bool eval_part = env_ep != 0 && (!ipc_fused || eb_ok) && eval_fg == 0 && ep_steps <= 8 && d.F <= 32;
+  // monotone constraints: one GPU, and the constrained evaluation is a kernel of its own (k_eval_mono), so
+  // no fused evaluation + partition pass (as COBALT_EVAL_PART=0)
+  const bool mono = c->mono_on;
+  if (mono && (dp || sampled)) return -16;
+  const bool eval_part = !mono && env_ep != 0 && (!ipc_fused || eb_ok) && eval_fg == 0 && ep_steps <= 8 && d.F <= 32;
   // A level's fused pass: {item rows (0: separate k_eval + k_partition), mode}. Every-block form: the
   // smallest item (1024-row steps from 4096) whose grid -- items + one partial item per node -- is one
   // block per CU (a second round of blocks doubles the level; 1.25M rows: 6144 at every level).
@@ -3607,18 +3746,26 @@ static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool s
       } else if (eval_fg > 0) {  // features in groups of eval_fg over several CUs, then a per-node reduction
         const int ng = ceil_div(d.F, eval_fg);
         const dim3 eg(1 << level, ng), eb(ceil_div(eval_fg, 2) * kWave);
-        if (d.ipc_epoch)
+        if (mono)
+          GLAUNCH("k_eval", (k_eval_mono<true>), eg, eb, 0, stream, d, level, parity, t, eval_fg, EvalSlots{}, c->mono);
+        else if (d.ipc_epoch)
           GLAUNCH("k_eval", (k_eval<true, true, true>), eg, eb, fused_lds, stream, d, level, parity, t, eval_fg, EvalSlots{});
         else if (dp)
           GLAUNCH("k_eval", (k_eval<true, false, true>), eg, eb, 0, stream, d, level, parity, t, eval_fg, EvalSlots{});
         else
           GLAUNCH("k_eval", (k_eval<true, false, false>), eg, eb, 0, stream, d, level, parity, t, eval_fg, EvalSlots{});
-        if (dp)
+        if (mono)
+          GLAUNCH("k_eval_finish", k_eval_finish_mono, dim3(1 << level), dim3(kWave), 0, stream, d, level, parity, ng,
+                  c->mono);
+        else if (dp)
           GLAUNCH("k_eval_finish", k_eval_finish<true>, dim3(1 << level), dim3(kWave), 0, stream, d, level, parity, ng);
         else
           GLAUNCH("k_eval_finish", k_eval_finish<false>, dim3(1 << level), dim3(kWave), 0, stream, d, level, parity, ng);
       } else {
-        if (d.ipc_epoch)
+        if (mono)
+          GLAUNCH("k_eval", (k_eval_mono<false>), dim3(1 << level), dim3(1024), 0, stream, d, level, parity, t, d.F,
+                  c->eval_slots, c->mono);
+        else if (d.ipc_epoch)
           GLAUNCH("k_eval", (k_eval<false, true, true>), dim3(1 << level), dim3(1024), fused_lds, stream, d, level, parity,
                   t, d.F, c->eval_slots);
         else if (dp)
@@ -4010,6 +4157,32 @@ COBALT_API int cobalt_gbdt_set_binary_labels(void* h, float spw, hipStream_t str
   return 0;
 }
 
+// Monotone constraints of this fit (after create / reuse, before the first grow call): `cons` = n_feat host
+// bytes in {-1, 0, +1}. All zeros (or a null pointer) leaves the fit unconstrained. Constrained fits run on one
+// GPU in core (grow returns -16 under a communicator or on a per-tree sample). The vector and the bounds
+// workspace are allocated once per context; cobalt_gbdt_reuse clears the state for the next fit.
+COBALT_API int cobalt_gbdt_set_monotone(void* h, const int8_t* cons, int n_feat) {
+  GbdtCtx* c = static_cast<GbdtCtx*>(h);
+  if (!c || n_feat != c->d.F) return -13;
+  bool any = false;
+  for (int f = 0; cons && f < n_feat; ++f) {
+    if (cons[f] < -1 || cons[f] > 1) return -13;
+    any = any || cons[f] != 0;
+  }
+  c->mono_on = false;
+  if (!any) return 0;
+  if (c->cfg.comm) return -16;
+  if (!c->mono.c) {
+    int rc;
+    if ((rc = dev_alloc(c, (void**)&c->mono.c, (size_t)n_feat))) return rc;
+    if ((rc = dev_alloc(c, (void**)&c->mono.bounds, (size_t)c->max_nodes * 2 * sizeof(double)))) return rc;
+  }
+  // (blocking copy: no kernel of this context is in flight between two fits, and every later grow call sees it)
+  CK(hipMemcpy(const_cast<int8_t*>(c->mono.c), cons, (size_t)n_feat, hipMemcpyHostToDevice));
+  c->mono_on = true;
+  return 0;
+}
+
 COBALT_API int cobalt_gbdt_set_start(void* h, int t0) {
   GbdtCtx* c = static_cast<GbdtCtx*>(h);
   if (t0 < 0 || t0 > c->cfg.max_trees || c->grown != 0) return -12;
@@ -4075,6 +4248,7 @@ COBALT_API int cobalt_gbdt_reuse(void* h, const GbdtConfig* cfg) {
   c->applied = 0;
   c->fit_first = 0;
   c->fault_tree = -1;
+  c->mono_on = false;  // (the next fit sets its own constraints, if any)
   if (c->err_pinned) memset(c->err_pinned, 0, 64);
   return 0;
 }

@@ -136,6 +136,13 @@ class Booster:
     def num_trees(self) -> int:
         return len(self.trees)
 
+    @property
+    def monotone_constraints(self) -> tuple[int, ...] | None:
+        """The monotone constraints the model was fitted under, one of {-1, 0, +1} per feature (None:
+        unconstrained)."""
+        v = self.train_params.get("monotone_constraints")
+        return tuple(int(c) for c in v) if v else None
+
     def slice(self, n_trees: int) -> "Booster":
         return Booster(self.trees[:n_trees], self.feature_names, self.feature_types, self.base_score,
                        self.num_feature, self.objective, dict(self.train_params), dict(self.attributes))
@@ -259,6 +266,7 @@ class Booster:
              "scale_pos_weight": 1.0, "seed": 0}
         p.update({k: v for k, v in self.train_params.items() if v is not None})
         f = _fmt_float
+        mono = self.monotone_constraints
         return {
             "learner": {
                 "generic_param": {"device": "cpu", "fail_on_invalid_gpu_id": "0", "n_jobs": "0", "nthread": "0",
@@ -279,7 +287,7 @@ class Booster:
                         "max_cat_threshold": "64", "max_cat_to_onehot": "4", "max_delta_step": "0",
                         "max_depth": str(int(p["max_depth"])), "max_leaves": "0",
                         "min_child_weight": f(p["min_child_weight"]), "min_split_loss": f(p["gamma"]),
-                        "monotone_constraints": "()", "refresh_leaf": "1", "reg_alpha": f(p["reg_alpha"]),
+                        "monotone_constraints": monotone_string(mono), "refresh_leaf": "1", "reg_alpha": f(p["reg_alpha"]),
                         "reg_lambda": f(p["reg_lambda"]), "sampling_method": "uniform", "sketch_ratio": "2",
                         "sparse_threshold": "0.20000000000000001", "subsample": f(p["subsample"])},
                     "updater": [{"hist_train_param": {"debug_synchronize": "0", "extmem_single_page": "0",
@@ -353,6 +361,9 @@ class Booster:
                               ("colsample_bytree", "colsample_bytree", float), ("max_bin", "max_bin", int)):
             if src in ttp:
                 params[dst] = typ(float(ttp[src]))
+        mono = parse_monotone_string(ttp.get("monotone_constraints", "()"))
+        if any(mono):
+            params["monotone_constraints"] = mono
         spw = lrn.get("objective", {}).get("reg_loss_param", {}).get("scale_pos_weight")
         if spw is not None:
             params["scale_pos_weight"] = float(spw)
@@ -395,6 +406,22 @@ class Booster:
         if p.suffix in (".pkl", ".pickle", ".joblib") or data[:1] == b"\x80":
             return load_pickle_bytes(data)[1]
         return cls.load_raw(data)
+
+
+def monotone_string(mono: Sequence[int] | None) -> str:
+    """XGBoost's string form of a constraint vector: ``"(1,0,-1)"``; ``"()"`` without constraints."""
+    return "(" + ",".join(str(int(c)) for c in mono) + ")" if mono else "()"
+
+
+def parse_monotone_string(s: str) -> tuple[int, ...]:
+    """``"(1,0,-1)"`` (parentheses optional) -> ``(1, 0, -1)``; ``"()"`` / ``""`` -> ``()``."""
+    body = s.strip()
+    if body.startswith("(") and body.endswith(")"):
+        body = body[1:-1]
+    try:
+        return tuple(int(tok) for tok in body.split(",") if tok.strip())
+    except ValueError:
+        raise ValueError(f"monotone_constraints: cannot parse {s!r} (expected a form like '(1,0,-1)')") from None
 
 
 def _jsonable(v: Any) -> Any:

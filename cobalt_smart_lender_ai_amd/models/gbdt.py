@@ -70,6 +70,10 @@ class GBDTParams:
     # ("wide": g and h summed in separate int64 cells, 256x finer steps; 32-byte records, <= 24 features
     # on the GPU; the CPU trainer implements both exactly -- docs/PERF.md "Gradient precision")
     grad_bits: int = 17
+    # monotone constraints (XGBoost's ``monotone_constraints``): a sequence of {-1, 0, +1} per feature, the
+    # string form "(1,0,-1)", or {feature_name: +-1} (resolved against the fit's feature names; unnamed
+    # features get 0). None / () / "()" / all zeros: the unconstrained fit. See :func:`resolve_monotone`.
+    monotone_constraints: Any = None
 
     @classmethod
     def from_kwargs(cls, **kw) -> "GBDTParams":
@@ -348,9 +352,11 @@ def subset_features(bd: BinnedData, feats) -> BinnedData:
 
 
 def expand_features(bst: Booster, feats, n_features: int, feature_names: Sequence[str] | None = None,
-                    feature_types: Sequence[str] | None = None) -> Booster:
+                    feature_types: Sequence[str] | None = None, monotone_constraints=None) -> Booster:
     """A booster fitted on :func:`subset_features` columns, re-expressed over the full feature space
-    (split indices mapped back; leaves keep index 0 as XGBoost writes them)."""
+    (split indices mapped back; leaves keep index 0 as XGBoost writes them). Its monotone constraints go
+    back to full width: ``monotone_constraints`` (the full vector) when given, else the subset's entries
+    at ``feats`` and 0 elsewhere."""
     from .booster import Tree
 
     f = np.asarray(feats, dtype=np.int32)
@@ -359,9 +365,68 @@ def expand_features(bst: Booster, feats, n_features: int, feature_names: Sequenc
         si = np.where(t.left_children != -1, f[t.split_indices], 0).astype(np.int32)
         trees.append(Tree(t.left_children, t.right_children, t.parents, si, t.split_conditions, t.default_left,
                           t.base_weights, t.loss_changes, t.sum_hessian))
+    tparams = dict(bst.train_params)
+    if monotone_constraints is not None:
+        tparams["monotone_constraints"] = tuple(int(c) for c in monotone_constraints)
+    elif bst.monotone_constraints is not None:
+        full = np.zeros(int(n_features), dtype=np.int8)
+        full[f] = bst.monotone_constraints
+        tparams["monotone_constraints"] = tuple(int(c) for c in full)
     return Booster(trees, list(feature_names) if feature_names is not None else None,
                    list(feature_types) if feature_types is not None else None, bst.base_score, int(n_features),
-                   bst.objective, dict(bst.train_params), dict(bst.attributes))
+                   bst.objective, tparams, dict(bst.attributes))
+
+
+def resolve_monotone(mc, n_features: int, feature_names: Sequence[str] | None = None) -> np.ndarray | None:
+    """``monotone_constraints`` in any accepted form -> int8 [n_features] in {-1, 0, +1}, or None for an
+    unconstrained fit (None, an empty form, all zeros). ``ValueError``: a length other than the feature
+    count, a value outside {-1, 0, 1}, a dict without feature names or with an unknown name."""
+    if mc is None:
+        return None
+    if isinstance(mc, dict):
+        if not mc:
+            return None
+        if feature_names is None:
+            raise ValueError("monotone_constraints given by feature name needs feature_names")
+        names = [str(n) for n in feature_names]
+        unknown = [k for k in mc if str(k) not in names]
+        if unknown:
+            raise ValueError(f"monotone_constraints names unknown features: {unknown}")
+        vals = [0] * len(names)
+        for k, v in mc.items():
+            vals[names.index(str(k))] = v
+    else:
+        vals = _mono_plain(mc)
+        if not vals:
+            return None
+    if len(vals) != n_features:
+        raise ValueError(f"monotone_constraints has {len(vals)} entries, the data has {n_features} features")
+    bad = [v for v in vals if isinstance(v, bool) or v not in (-1, 0, 1)]
+    if bad:
+        raise ValueError(f"monotone_constraints values must be -1, 0 or 1 (got {bad[0]!r})")
+    vec = np.asarray([int(v) for v in vals], dtype=np.int8)
+    return vec if vec.any() else None
+
+
+def _refuse_monotone(params: "GBDTParams", what: str) -> None:
+    """Constrained fits run on one device, in core: every other trainer refuses the argument by name."""
+    mc = getattr(params, "monotone_constraints", None)
+    if mc is None:
+        return
+    plain = _mono_plain(mc)
+    if any(mc.values()) if plain is None else any(plain):
+        raise ValueError(f"monotone_constraints is not supported {what}")
+
+
+def _mono_plain(mc) -> list | None:
+    """The sequence / string forms as a plain list (None for a dict)."""
+    from .booster import parse_monotone_string
+
+    if isinstance(mc, dict):
+        return None
+    if isinstance(mc, str):
+        return list(parse_monotone_string(mc))
+    return list(np.asarray(mc).reshape(-1).tolist())
 
 
 def check_grad_bits(grad_bits: int, n_features: int, device_type: str) -> None:
@@ -513,6 +578,8 @@ def train(X, y, params: GBDTParams | dict | None = None, *, sample_weight=None, 
     elif isinstance(params, dict):
         params = GBDTParams.from_kwargs(**params)
     t0 = time.perf_counter()
+    if dist is not None:
+        _refuse_monotone(params, "in data-parallel fits (dist)")
     evals = _eval_monitor(evals, eval_metric, early_stopping_rounds, _resolve_device(device, X), int(X.shape[1]),
                           dist, checkpoint_path is not None, verbose_eval)
     ckpt = Checkpointer(checkpoint_path, checkpoint_every, params, dist) if checkpoint_path else None
@@ -576,6 +643,10 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
         raise ValueError("es_segment must be >= 1")
     grad_bits = int(params.grad_bits)
     N, F = bd.n_rows, bd.n_features
+    if dist is not None:
+        _refuse_monotone(params, "in data-parallel fits (dist)")
+    mono = resolve_monotone(params.monotone_constraints, F, feature_names if feature_names is not None else (
+        init_booster.feature_names if init_booster is not None else None))
     check_grad_bits(grad_bits, F, dev.type)
     if dev.type == "cuda":
         check_gpu_shape(int(params.max_depth), N)
@@ -658,7 +729,9 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
                                          min_child_weight=hp.min_child_weight, reg_lambda=hp.reg_lambda,
                                          reg_alpha=hp.reg_alpha, subsample=hp.subsample,
                                          colsample_bytree=float(params.colsample_bytree),
-                                         max_bin=int(params.max_bin), scale_pos_weight=spw, seed=hp.seed))
+                                         max_bin=int(params.max_bin), scale_pos_weight=spw, seed=hp.seed,
+                                         **({"monotone_constraints": tuple(int(c) for c in mono)}
+                                            if mono is not None else {})))
 
     def early_stop(s0: int) -> bool:
         """Early stopping: score the segment's trees (rounds s0 ...); on a stop keep trees 0..that round."""
@@ -688,7 +761,7 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
                                   gamma=float(params.gamma), min_child_weight=float(params.min_child_weight),
                                   subsample=float(params.subsample), seed=int(params.random_state),
                                   gscale=1.0 if exact_fp64 else gscale, hscale=1.0 if exact_fp64 else hscale,
-                                  quant=not exact_fp64, qbits=grad_bits)
+                                  quant=not exact_fp64, qbits=grad_bits, monotone=mono)
     if exact_fp64 and dev.type != "cpu":
         raise ValueError("exact_fp64 is the host (CPU) reference trainer")
     tp = rep.mark("labels_weights", tp, dev)
@@ -716,6 +789,8 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
                 and bd.records.shape[1] == 32 and F <= 23
                 and (labels_binary if labels_binary is not None else bool(((yt == 0) | (yt == 1)).all()))):
             tr.set_binary_labels(float(np.float32(spw)))
+        if mono is not None:  # (a reused context starts every fit unconstrained: cobalt_gbdt_reuse)
+            tr.set_monotone(mono)
         tp = rep.mark("trainer_setup", tp, dev)
         completed = False
         try:
@@ -880,7 +955,16 @@ class Checkpointer:
     def _meta(self, n_trees: int) -> dict:
         keys = ("max_depth", "learning_rate", "gamma", "min_child_weight", "reg_lambda", "reg_alpha", "subsample",
                 "colsample_bytree", "max_bin", "scale_pos_weight", "random_state", "n_estimators")
-        return {"n_trees": n_trees, "params": {k: getattr(self.params, k) for k in keys}}
+        meta = {"n_trees": n_trees, "params": {k: getattr(self.params, k) for k in keys}}
+        # (None without constraints, whatever the form: a checkpoint from before the parameter resumes)
+        mc = self.params.monotone_constraints
+        if isinstance(mc, dict):
+            mc = {str(k): int(v) for k, v in sorted(mc.items()) if int(v)} or None
+        elif mc is not None:
+            plain = _mono_plain(mc)
+            mc = [int(v) for v in plain] if any(plain) else None
+        meta["params"]["monotone_constraints"] = mc
+        return meta
 
     def save(self, booster: Booster) -> None:
         if self.rank != 0:
@@ -931,13 +1015,13 @@ class GBDTClassifier:
     _param_names = ["n_estimators", "max_depth", "learning_rate", "gamma", "min_child_weight", "reg_lambda",
                     "reg_alpha", "subsample", "colsample_bytree", "max_bin", "scale_pos_weight", "random_state",
                     "base_score", "eval_metric", "use_label_encoder", "device", "importance_type", "n_jobs",
-                    "sketch_rows", "sketch_weight", "early_stopping_rounds"]
+                    "sketch_rows", "sketch_weight", "early_stopping_rounds", "monotone_constraints"]
 
     def __init__(self, n_estimators=None, max_depth=None, learning_rate=None, gamma=None, min_child_weight=None,
                  reg_lambda=None, reg_alpha=None, subsample=None, colsample_bytree=None, max_bin=None,
                  scale_pos_weight=None, random_state=None, base_score=None, eval_metric=None,
                  use_label_encoder=None, device=None, importance_type=None, n_jobs=None, sketch_rows=None,
-                 sketch_weight=None, early_stopping_rounds=None):
+                 sketch_weight=None, early_stopping_rounds=None, monotone_constraints=None):
         self.n_estimators = n_estimators
         self.max_depth = max_depth
         self.learning_rate = learning_rate
@@ -959,10 +1043,14 @@ class GBDTClassifier:
         self.sketch_rows = sketch_rows
         self.sketch_weight = sketch_weight
         self.early_stopping_rounds = early_stopping_rounds
+        self.monotone_constraints = monotone_constraints
 
     # sklearn protocol
     def get_params(self, deep: bool = True) -> dict[str, Any]:
-        return {k: getattr(self, k) for k in self._param_names}
+        # ``monotone_constraints`` is listed when it is set (``clone`` / ``set_params`` carry it); an estimator
+        # without constraints reports exactly the parameters it reported before the argument existed
+        return {k: getattr(self, k) for k in self._param_names
+                if k != "monotone_constraints" or self.monotone_constraints is not None}
 
     def set_params(self, **params) -> "GBDTClassifier":
         for k, v in params.items():
@@ -1119,7 +1207,13 @@ class GBDTClassifier:
         p = {k: getattr(self, k) for k in ["n_estimators", "max_depth", "learning_rate", "gamma", "min_child_weight",
                                            "reg_alpha", "reg_lambda", "subsample", "colsample_bytree",
                                            "scale_pos_weight", "base_score", "random_state", "max_bin", "device",
-                                           "importance_type", "n_jobs", "eval_metric", "early_stopping_rounds"]}
+                                           "importance_type", "n_jobs", "eval_metric", "early_stopping_rounds",
+                                           "monotone_constraints"]}
+        mc = p["monotone_constraints"]
+        if mc is not None and not isinstance(mc, (str, dict)):  # a sequence is written in XGBoost's string form
+            from .booster import monotone_string
+
+            p["monotone_constraints"] = monotone_string(_mono_plain(mc))
         p["kwargs"] = {"use_label_encoder": self.use_label_encoder} if self.use_label_encoder is not None else {}
         return p
 

@@ -85,6 +85,9 @@ class HostGbdtParams:
     hscale: float
     quant: bool = True   # False: unquantised fp64 gradients and histograms (accuracy reference)
     qbits: int = QBITS   # quantised magnitude bits: 17, or 25 (wide gradients)
+    # monotone constraints: int8 [F] in {-1, 0, +1} (None: unconstrained). Constrained mode: every node
+    # carries fp64 weight bounds [lo, hi] (root: -inf, +inf), see _eval_node_mono / grow_tree_host
+    monotone: np.ndarray | None = None
 
 
 def quant_scales(w_max: float, bits: int = QBITS) -> tuple[float, float]:
@@ -123,6 +126,26 @@ def _calc_weight(g: float, h: float, lam: float, alpha: float, mcw: float) -> fl
         return 0.0
     t = g if alpha == 0.0 else float(_thresh_l1(np.float64(g), alpha))
     return -t / (h + lam)
+
+
+def _clamp(w, lo, hi):
+    """min(max(w, lo), hi) by compare-and-select (the device's form: a zero keeps its sign)."""
+    w = np.where(w < lo, lo, w)
+    return np.where(w > hi, hi, w)
+
+
+def _calc_weight_mono(g, h, lam, alpha, mcw, lo, hi):
+    """Bounded node weight (arrays or scalars): ``_calc_weight`` clamped to [lo, hi] afterwards."""
+    t = g if alpha == 0.0 else _thresh_l1(g, alpha)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = np.where((h < mcw) | (h <= 0.0), 0.0, -t / (h + lam))
+    return _clamp(w, lo, hi)
+
+
+def _gain_given_weight(g, h, w, lam, alpha):
+    """-(2 t w + (h + lambda) w^2), in the device's operation order (csrc/gbdt.hip, gain_given_weight)."""
+    t = g if alpha == 0.0 else _thresh_l1(g, alpha)
+    return -(2.0 * t * w + (h + lam) * w * w)
 
 
 def gradients_host(margin: np.ndarray, label: np.ndarray, weight: np.ndarray, p: HostGbdtParams, tree: int,
@@ -171,8 +194,10 @@ def _node_hist(bins, rows, gq, hq, fmask, nbins=None) -> np.ndarray:
     return out
 
 
-def _eval_node(hist, G, H, nbins, fmask, p: HostGbdtParams):
+def _eval_node(hist, G, H, nbins, fmask, p: HostGbdtParams, lo: float = -np.inf, hi: float = np.inf):
     """Best split of one node: returns (gain, key, GL, HL) or None."""
+    if p.monotone is not None:
+        return _eval_node_mono(hist, G, H, nbins, fmask, p, lo, hi)
     ginv, hinv = 1.0 / p.gscale, 1.0 / p.hscale
     Gd, Hd = G * ginv, H * hinv
     pg = float(_calc_gain(np.float64(Gd), np.float64(Hd), p.reg_lambda, p.reg_alpha, p.min_child_weight))
@@ -213,6 +238,59 @@ def _eval_node(hist, G, H, nbins, fmask, p: HostGbdtParams):
     return (best_gain, best_key, best_gl, best_hl), Gd, Hd
 
 
+def _eval_node_mono(hist, G, H, nbins, fmask, p: HostGbdtParams, lo: float, hi: float):
+    """``_eval_node`` under monotone constraints (node bounds [lo, hi]): every candidate's children take
+    their bounded weights ``wl`` / ``wr``; a candidate on a constrained feature whose weights are in the
+    wrong order is rejected; the gain is the gain GIVEN those weights. Same enumeration order, filter,
+    arg-max and tie-break. Returns ((gain, key, GL, HL, wl, wr) or None, Gd, Hd)."""
+    ginv, hinv = 1.0 / p.gscale, 1.0 / p.hscale
+    lam, alpha, mcw = p.reg_lambda, p.reg_alpha, p.min_child_weight
+    Gd, Hd = G * ginv, H * hinv
+    Ga, Ha = np.float64(Gd), np.float64(Hd)
+    pg = 0.0 if Hd < mcw else float(_gain_given_weight(Ga, Ha, _calc_weight_mono(Ga, Ha, lam, alpha, mcw, lo, hi),
+                                                       lam, alpha))
+    best_gain, best_key, best = -np.inf, np.iinfo(np.int32).max, None
+    F = len(nbins)
+    for f in range(F):
+        if not fmask[f]:
+            continue
+        c = int(p.monotone[f])
+        nb = int(nbins[f])
+        hg, hh = hist[f, :, 0], hist[f, :, 1]
+        cg, ch = np.cumsum(hg), np.cumsum(hh)
+        mg, mh = G - cg[-1].item(), H - ch[-1].item()
+        b = np.arange(nb)
+        cands = [(cg[:nb], ch[:nb], f * 1024 + b)]
+        has_missing = mg != 0 or mh != 0 if p.quant else (F >= 255 or hist[F, 1 + f, 0] > 0)
+        if has_missing:
+            cands.append((cg[:nb] - hg[:nb] + mg, ch[:nb] - hh[:nb] + mh, f * 1024 + 512 + (nb - 1 - b)))
+        for GL, HL, key in cands:
+            gl = GL.astype(np.float64) * ginv
+            hl = HL.astype(np.float64) * hinv
+            gr = (G - GL).astype(np.float64) * ginv
+            hr = (H - HL).astype(np.float64) * hinv
+            ok = (hl >= mcw) & (hr >= mcw)
+            if not ok.any():
+                continue
+            wl = _calc_weight_mono(gl, hl, lam, alpha, mcw, lo, hi)
+            wr = _calc_weight_mono(gr, hr, lam, alpha, mcw, lo, hi)
+            if c > 0:
+                ok &= ~(wl > wr)
+            elif c < 0:
+                ok &= ~(wl < wr)
+            gain = _gain_given_weight(gl, hl, wl, lam, alpha) + _gain_given_weight(gr, hr, wr, lam, alpha) - pg
+            gain = np.where(ok, gain, -np.inf)
+            mx = gain.max()
+            if mx == -np.inf:
+                continue
+            sel = np.nonzero(gain == mx)[0]
+            i = sel[np.argmin(key[sel])]
+            if mx > best_gain or (mx == best_gain and key[i] < best_key):
+                best_gain, best_key = float(mx), int(key[i])
+                best = (best_gain, best_key, GL[i].item(), HL[i].item(), float(wl[i]), float(wr[i]))
+    return best, Gd, Hd
+
+
 def grow_tree_host(bins: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, gq: np.ndarray, hq: np.ndarray,
                    margin: np.ndarray, p: HostGbdtParams, fmask: np.ndarray, allreduce=None) -> np.ndarray:
     """Grow one depthwise tree in place of ``margin`` (float32, updated with leaf values).
@@ -230,6 +308,9 @@ def grow_tree_host(bins: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, gq: np
     nodes[0]["build"] = 1
     nodes[0]["count"] = N
     GH = np.zeros((max_nodes, 2), dtype=np.int64 if p.quant else np.float64)  # node (G, H) sums
+    mono = p.monotone is not None
+    bounds = np.empty((max_nodes, 2), dtype=np.float64)  # monotone constraints: node weight bounds [lo, hi]
+    bounds[:, 0], bounds[:, 1] = -np.inf, np.inf
     rows: dict[int, np.ndarray] = {0: np.arange(N, dtype=np.int64)}
     hist_prev: dict[int, np.ndarray] = {}
     for level in range(D + 1):
@@ -272,10 +353,12 @@ def grow_tree_host(bins: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, gq: np
                 continue
             G, H = GH[n, 0].item(), GH[n, 1].item()
             if level < D:
-                best, Gd, Hd = _eval_node(hist_cur[n], G, H, nbins, fmask, p)
+                best, Gd, Hd = _eval_node(hist_cur[n], G, H, nbins, fmask, p, bounds[n, 0], bounds[n, 1])
             else:
                 best, Gd, Hd = None, G * (1.0 / p.gscale), H * (1.0 / p.hscale)
             wgt = _calc_weight(Gd, Hd, p.reg_lambda, p.reg_alpha, p.min_child_weight)
+            if mono:
+                wgt = float(_clamp(np.float64(wgt), bounds[n, 0], bounds[n, 1]))
             nodes[n]["sum_hess"] = np.float32(Hd)
             nodes[n]["base_weight"] = np.float32(wgt * p.eta)
             ok = False
@@ -284,7 +367,7 @@ def grow_tree_host(bins: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, gq: np
                 ok = bool(loss > np.float32(1e-6) and loss >= np.float32(p.gamma))
             r = rows.get(n, np.zeros(0, np.int64))
             if ok:
-                gain, key, GL, HL = best
+                gain, key, GL, HL = best[:4]
                 f = key >> 10
                 rr = key & 1023
                 nb = int(nbins[f])
@@ -302,6 +385,12 @@ def grow_tree_host(bins: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, gq: np
                 nodes[L]["status"], nodes[R]["status"] = 1, 1
                 GH[L] = (GL, HL)
                 GH[R] = (G - GL, H - HL)
+                if mono:  # children's bounds: the midpoint of the winner's weights separates them
+                    lo, hi = bounds[n]
+                    mid = (best[4] + best[5]) / 2
+                    c = int(p.monotone[f])
+                    bounds[L] = (lo, mid) if c > 0 else ((mid, hi) if c < 0 else (lo, hi))
+                    bounds[R] = (mid, hi) if c > 0 else ((lo, mid) if c < 0 else (lo, hi))
                 b = bins[r, f]
                 go_left = np.where(b == 255, dl == 1, b.astype(np.int64) <= j)
                 rows[L] = r[go_left]

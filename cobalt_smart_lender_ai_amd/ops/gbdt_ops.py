@@ -211,6 +211,15 @@ class GpuGbdtTrainer:
         _native.check(rc, "cobalt_gbdt_set_binary_labels")
         return True
 
+    def set_monotone(self, constraints: np.ndarray) -> None:
+        """Monotone constraints of this fit (int8 [n_feat] in {-1, 0, +1}), before the first :meth:`grow`.
+        Constrained fits run on one GPU; a context taken from the cache starts unconstrained."""
+        c = np.ascontiguousarray(constraints, dtype=np.int8)
+        rc = self.lib.cobalt_gbdt_set_monotone(self.h, c.ctypes.data, int(c.shape[0]))
+        if rc == -16:
+            raise ValueError("monotone_constraints is not supported in data-parallel fits")
+        _native.check(rc, "cobalt_gbdt_set_monotone")
+
     def plan(self) -> dict:
         """The last grow call's launch plan (csrc/gbdt.hip cobalt_gbdt_plan)."""
         fn = getattr(self.lib, "cobalt_gbdt_plan", None)

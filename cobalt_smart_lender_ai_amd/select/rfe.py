@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import logging
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -58,14 +58,19 @@ def rfe(X, y, params: gbdt.GBDTParams | dict, n_features_to_select: int = 20, st
     if bd.device.type == "cuda":  # labels go to the device once, not once per fit
         yt = gbdt._to_tensor(y, bd.device).reshape(-1)
 
+    # monotone constraints, resolved once over the full width (a dict may name a feature that a later
+    # step eliminates); a repacked fit takes the survivors' entries
+    mono = gbdt.resolve_monotone(params.monotone_constraints, F, feature_names)
+
     def fit(sup: np.ndarray):
         feats = np.nonzero(sup)[0]
         if not repack or len(feats) == F:
             return gbdt.train_binned(bd, yt, params, feature_mask=sup, feature_names=feature_names)
         sub = gbdt.subset_features(bd, feats)
         names = [feature_names[i] for i in feats] if feature_names is not None else None
-        b = gbdt.train_binned(sub, yt, params, feature_names=names)
-        return gbdt.expand_features(b, feats, F, feature_names)
+        sub_params = params if mono is None else replace(params, monotone_constraints=tuple(int(c) for c in mono[feats]))
+        b = gbdt.train_binned(sub, yt, sub_params, feature_names=names)
+        return gbdt.expand_features(b, feats, F, feature_names, monotone_constraints=mono)
 
     while support.sum() > n_features_to_select:
         feats = np.nonzero(support)[0]
