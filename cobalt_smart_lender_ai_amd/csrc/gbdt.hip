@@ -1589,15 +1589,31 @@ __device__ __forceinline__ double calc_weight(double g, double h, double lambda_
 // candidate's gain is the gain GIVEN its children's weights, a candidate on a constrained feature
 // whose weights are in the wrong order is rejected, and the children of a split on a constrained feature
 // take the midpoint of the winner's weights as their common bound. The constrained kernels take the
-// constraint vector and the bounds as one more argument; the unconstrained instantiations carry an
-// empty struct instead (same code as without the feature).
+// constraint vector and the bounds as one more argument (ConsDev below); the unconstrained
+// instantiations carry an empty struct instead (same code as without the feature).
 struct MonoDev {
   const int8_t* c;  // [F] constraint per feature: -1, 0, +1
   double* bounds;   // [max_nodes][2] (lo, hi); written by eval_finalize for the children of a split
 };
-struct MonoNone {};
-template <bool kMono>
-using MonoArg = typename std::conditional<kMono, MonoDev, MonoNone>::type;
+// Interaction constraints (XGBoost's interaction_constraints; models/gbdt_host.py grow_tree_host is the
+// specification). A constraint is a list of <= 64 feature groups: feature f carries the word fgroups[f]
+// (bit k: f is in group k), node n the word compat[n] (bit k: group k holds every feature split on along
+// the path to n). The root evaluates every feature; below it feature g is evaluated at n iff
+// compat[n] & fgroups[g] != 0 (one AND with wave-uniform state, folded into EvalFeat::on next to the
+// colsample bit), and a split of n on f gives both children compat[n] & fgroups[f] (the root: fgroups[f]).
+// Like the bounds, the words live in a workspace array of the context, not in Node.
+struct InterDev {
+  const uint64_t* fgroups;  // [F] group membership per feature
+  uint64_t* compat;         // [max_nodes]; written by eval_finalize for the children of a split
+};
+// The constrained kernels' extra argument (monotone, interaction or both: the unused half is null)
+struct ConsDev {
+  MonoDev mono;
+  InterDev inter;
+};
+struct ConsNone {};
+template <bool kCons>
+using ConsArg = typename std::conditional<kCons, ConsDev, ConsNone>::type;
 
 // min(max(w, lo), hi) by compare-and-select: a zero keeps its sign (as the host's _clamp)
 __device__ __forceinline__ double mono_clamp(double w, double lo, double hi) {
@@ -1632,9 +1648,10 @@ struct EvalFeat {
 // kMono: the node's weight is clamped to its bounds, a split writes its children's bounds (the winner's
 // weights are recomputed from the children's sums: the same fp64 values the candidate was scored with)
 // and the max-depth leaves take the bounds just computed.
-template <bool kDP, bool kMono = false>
+// kInter: a split writes its children's compat word (the node's AND the split feature's groups).
+template <bool kDP, bool kMono = false, bool kInter = false>
 __device__ void eval_finalize(const GbdtDev& d, int level, int n, int64_t G, int64_t H, Cand best, float best_cut,
-                              int nb_known = -1, MonoArg<kMono> mono = {}) {
+                              int nb_known = -1, ConsArg<kMono || kInter> cons = {}) {
   Node* nodes = d.nodes;
   const double Gd = (double)G * d.ginv, Hd = (double)H * d.hinv;
   const float loss = (float)best.gain;
@@ -1643,6 +1660,7 @@ __device__ void eval_finalize(const GbdtDev& d, int level, int n, int64_t G, int
   double blo = -INFINITY, bhi = INFINITY;        // kMono: this node's bounds (the root's are the whole line)
   double clo[2] = {blo, blo}, chi[2] = {bhi, bhi};  // ... and its children's (L, R)
   if constexpr (kMono) {
+    const MonoDev& mono = cons.mono;
     if (level == 0) {  // the root's entry is reset with every tree
       mono.bounds[0] = blo;
       mono.bounds[1] = bhi;
@@ -1651,6 +1669,11 @@ __device__ void eval_finalize(const GbdtDev& d, int level, int n, int64_t G, int
       bhi = mono.bounds[2 * n + 1];
     }
     wgt = mono_clamp(wgt, blo, bhi);
+  }
+  uint64_t compat = ~0ull;  // kInter: the groups holding this node's path (the root's: all of them)
+  if constexpr (kInter) {
+    if (level == 0) cons.inter.compat[0] = compat;  // reset with every tree
+    else compat = cons.inter.compat[n];
   }
   Node& nd = nodes[n];
   if (level == 0) { nd.G = G; nd.H = H; }
@@ -1678,7 +1701,13 @@ __device__ void eval_finalize(const GbdtDev& d, int level, int n, int64_t G, int
     const int lb = best.hl <= H - best.hl ? 1 : 0;
     L.build = lb;
     R.build = 1 - lb;
+    if constexpr (kInter) {
+      const uint64_t cc = compat & cons.inter.fgroups[f];
+      cons.inter.compat[2 * n + 1] = cc;
+      cons.inter.compat[2 * n + 2] = cc;
+    }
     if constexpr (kMono) {
+      const MonoDev& mono = cons.mono;
       const double wl = calc_weight_mono((double)best.gl * d.ginv, (double)best.hl * d.hinv, d.lambda_, d.alpha, d.mcw,
                                          blo, bhi);
       const double wr = calc_weight_mono((double)(G - best.gl) * d.ginv, (double)(H - best.hl) * d.hinv, d.lambda_,
@@ -1964,11 +1993,13 @@ struct EvalOut {
 // kDP: data parallel (kFused implies it): the level-0 replica-digest check and the fault-injection hook;
 // the single-GPU instantiation carries neither.
 // kMono (one GPU, no exchange): monotone constraints -- candidates are scored by score_mono below.
-template <bool kGroups, bool kFused, bool kDP, bool kMerged = false, bool kMono = false>
+// kInter (likewise): interaction constraints -- below the root a feature is evaluated iff one of its groups
+// holds the node's path (EvalFeat::on); scores, order and arg-max are those of the unconstrained code.
+template <bool kGroups, bool kFused, bool kDP, bool kMerged = false, bool kMono = false, bool kInter = false>
 __device__ __forceinline__ bool eval_core(const GbdtDev& d, int level, int parity, int tree, int fg, const EvalSlots& es,
                                           int pos, BlockStamp& stamp_, EvalOut* s_out, bool store_hist = true,
-                                          MonoArg<kMono> mono = {}) {
-  static_assert(!kMono || (!kFused && !kDP && !kMerged), "constrained fits run on one GPU, unfused");
+                                          ConsArg<kMono || kInter> cons = {}) {
+  static_assert(!(kMono || kInter) || (!kFused && !kDP && !kMerged), "constrained fits run on one GPU, unfused");
   const int fbeg = kGroups ? blockIdx.y * fg : 0;
   const int fend = kGroups ? min(d.F, fbeg + fg) : d.F;
   const int n = (1 << level) - 1 + pos;
@@ -1984,6 +2015,7 @@ __device__ __forceinline__ bool eval_core(const GbdtDev& d, int level, int parit
   // Per-feature metadata (mask, bin count, compact offset, cut values) does not depend on the node:
   // it is loaded in the same round trip as the node record (unconditional, in-bounds loads).
   EvalFeat ef[2];
+  uint64_t fgw[2] = {0, 0};  // kInter: the features' group words, loaded with the metadata
   auto load_meta = [&](int fbase) {
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -2008,6 +2040,7 @@ __device__ __forceinline__ bool eval_core(const GbdtDev& d, int level, int parit
       e.on = valid && fmv != 0;
       e.nb = valid ? nbv : 0;
       e.off = offv;
+      if constexpr (kInter) fgw[s] = cons.inter.fgroups[fc];
 #pragma unroll
       for (int c = 0; c < 4; ++c) e.cut[c] = d.cuts[fc * kMaxBins + c * kWave + lane];
     }
@@ -2078,6 +2111,12 @@ __device__ __forceinline__ bool eval_core(const GbdtDev& d, int level, int parit
     rh = hb[(int64_t)d.ncells * 2 + 1];
   }
   const int64_t ng = nodes[n].G, nh = nodes[n].H;
+  if constexpr (kInter) {  // the node's compat word: uniform address, in the round trip of the node record
+    // (the root evaluates every feature, the ungrouped ones too)
+    const uint64_t cm = level > 0 ? (uint64_t)readlane64((int64_t)cons.inter.compat[n], 0) : 0;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) ef[s].on = ef[s].on && (level == 0 || (cm & fgw[s]) != 0);
+  }
   int cb = 0;  // kFused: the block's first cell (LDS slot 0)
   if (kFused) {
     const IpcFusedView* iv = d.ipcv + (d.ipc_epoch & 1u);
@@ -2134,6 +2173,7 @@ __device__ __forceinline__ bool eval_core(const GbdtDev& d, int level, int parit
   // parent_gain, wave-uniform values pinned to SGPRs
   double blo = -INFINITY, bhi = INFINITY;
   if constexpr (kMono) {
+    const MonoDev& mono = cons.mono;
     if (level > 0) {
       blo = __longlong_as_double(readlane64(__double_as_longlong(mono.bounds[2 * n]), 0));
       bhi = __longlong_as_double(readlane64(__double_as_longlong(mono.bounds[2 * n + 1]), 0));
@@ -2190,7 +2230,7 @@ __device__ __forceinline__ bool eval_core(const GbdtDev& d, int level, int parit
     const int f = e.f, nb = e.nb;
     const int nch = (nb + kWave - 1) / kWave;  // wave-uniform
     int cf = 0;  // kMono: this feature's constraint (wave-uniform)
-    if constexpr (kMono) cf = __builtin_amdgcn_readfirstlane((int)mono.c[__builtin_amdgcn_readfirstlane(f)]);
+    if constexpr (kMono) cf = __builtin_amdgcn_readfirstlane((int)cons.mono.c[__builtin_amdgcn_readfirstlane(f)]);
     if (active && store_hist && level + 1 < d.max_depth) {  // this node's histogram, for its children's subtraction
       longlong2* hs2 = reinterpret_cast<longlong2*>(hs);
 #pragma unroll
@@ -2343,15 +2383,18 @@ __global__ __launch_bounds__(1024) void k_eval(GbdtDev d, int level, int parity,
   stamp_.probe(4);
 }
 
-// k_eval<kGroups, false, false> under monotone constraints (one GPU): the constraint vector and the nodes'
-// bounds are one more argument, so the unconstrained kernels keep their argument list.
-template <bool kGroups>
+// k_eval<kGroups, false, false> under monotone constraints, interaction constraints or both (one GPU):
+// the constraints and the nodes' state are one more argument, so the unconstrained kernels keep their
+// argument list. (kMono && !kInter is the monotone kernel as it was; the name is kept.)
+template <bool kGroups, bool kMono = true, bool kInter = false>
 __global__ __launch_bounds__(1024) void k_eval_mono(GbdtDev d, int level, int parity, int tree, int fg, EvalSlots es,
-                                                    MonoDev mono) {
+                                                    ConsDev cons) {
+  static_assert(kMono || kInter, "a constrained kernel");
   BlockStamp stamp_(d);
   const int pos = blockIdx.x;
   __shared__ EvalOut s_out;
-  if (!eval_core<kGroups, false, false, false, true>(d, level, parity, tree, fg, es, pos, stamp_, &s_out, true, mono))
+  if (!eval_core<kGroups, false, false, false, kMono, kInter>(d, level, parity, tree, fg, es, pos, stamp_, &s_out, true,
+                                                              cons))
     return;
   if (threadIdx.x != 0) return;  // thread 0 wrote s_out
   const Cand best = s_out.best;
@@ -2364,14 +2407,15 @@ __global__ __launch_bounds__(1024) void k_eval_mono(GbdtDev d, int level, int pa
     o.hl = best.hl;
     return;
   }
-  eval_finalize<false, true>(d, level, (1 << level) - 1 + pos, s_out.G, s_out.H, best, s_out.cut, s_out.nb, mono);
+  eval_finalize<false, kMono, kInter>(d, level, (1 << level) - 1 + pos, s_out.G, s_out.H, best, s_out.cut, s_out.nb,
+                                      cons);
   stamp_.probe(4);
 }
 
 // Reduce the per-group candidates of each node of the level (one wave per node, lane = group).
-template <bool kDP, bool kMono = false>
+template <bool kDP, bool kMono = false, bool kInter = false>
 __device__ __forceinline__ void eval_finish_node(const GbdtDev& d, int level, int parity, int ngroups,
-                                                 MonoArg<kMono> mono = {}) {
+                                                 ConsArg<kMono || kInter> cons = {}) {
   const int pos = blockIdx.x;
   const int n = (1 << level) - 1 + pos;
   const Node& nd = d.nodes[n];
@@ -2397,7 +2441,7 @@ __device__ __forceinline__ void eval_finish_node(const GbdtDev& d, int level, in
     best_cut = c.cut;
   }
   wave_best(best, best_cut);
-  if (lane == 0) eval_finalize<kDP, kMono>(d, level, n, G, H, best, best_cut, -1, mono);
+  if (lane == 0) eval_finalize<kDP, kMono, kInter>(d, level, n, G, H, best, best_cut, -1, cons);
 }
 
 template <bool kDP>
@@ -2406,9 +2450,10 @@ __global__ __launch_bounds__(64) void k_eval_finish(GbdtDev d, int level, int pa
   eval_finish_node<kDP>(d, level, parity, ngroups);
 }
 
-__global__ __launch_bounds__(64) void k_eval_finish_mono(GbdtDev d, int level, int parity, int ngroups, MonoDev mono) {
+template <bool kMono = true, bool kInter = false>
+__global__ __launch_bounds__(64) void k_eval_finish_mono(GbdtDev d, int level, int parity, int ngroups, ConsDev cons) {
   BlockStamp stamp_(d);
-  eval_finish_node<false, true>(d, level, parity, ngroups, mono);
+  eval_finish_node<false, kMono, kInter>(d, level, parity, ngroups, cons);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3070,7 +3115,10 @@ struct GbdtCtx {
   // monotone constraints of the current fit (cobalt_gbdt_set_monotone; cleared by cobalt_gbdt_reuse): the
   // constraint vector and the nodes' weight bounds, allocated on first use and kept with the context
   bool mono_on = false;
-  MonoDev mono{};
+  // interaction constraints of the current fit (cobalt_gbdt_set_interaction), handled like the monotone
+  // ones: the features' group words and the nodes' compat words (cons.inter)
+  bool inter_on = false;
+  ConsDev cons{};
   // the last grow call's plan (cobalt_gbdt_plan): fused IPC exchange, ownership level, wide gradients,
   // resident blocks of the fused k_eval, levels run by the fused evaluation + partition pass (and of them
   // the evaluator-block levels, and those whose grid exceeds one block per CU)
@@ -3103,6 +3151,20 @@ static int stamp_next(GbdtCtx* c, const char* name) {
   do {                                  \
     c->d.seq = stamp_next(c, tag);      \
     hipLaunchKernelGGL(__VA_ARGS__);    \
+  } while (0)
+// The constrained kernels' instantiation for the fit: monotone, interaction or both (arguments as GLAUNCH's
+// after the kernel).
+#define CONS_EVAL(kGroups, ...)                                                                        \
+  do {                                                                                                 \
+    if (c->mono_on && c->inter_on) GLAUNCH("k_eval", (k_eval_mono<kGroups, true, true>), __VA_ARGS__); \
+    else if (c->inter_on) GLAUNCH("k_eval", (k_eval_mono<kGroups, false, true>), __VA_ARGS__);         \
+    else GLAUNCH("k_eval", (k_eval_mono<kGroups, true, false>), __VA_ARGS__);                          \
+  } while (0)
+#define CONS_FINISH(...)                                                                                     \
+  do {                                                                                                       \
+    if (c->mono_on && c->inter_on) GLAUNCH("k_eval_finish", (k_eval_finish_mono<true, true>), __VA_ARGS__);  \
+    else if (c->inter_on) GLAUNCH("k_eval_finish", (k_eval_finish_mono<false, true>), __VA_ARGS__);          \
+    else GLAUNCH("k_eval_finish", (k_eval_finish_mono<true, false>), __VA_ARGS__);                           \
   } while (0)
 
 // Trees whose launches are stamped: every 64th from tree 5 (and tree 0 of short fits).
@@ -3614,9 +3676,9 @@ static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool s
     l0 = std::max(l0, D - 3);
     d.own_level = l0 < D ? l0 : -1;
   }
-  // monotone constraints: one GPU, and the constrained evaluation is a kernel of its own (k_eval_mono), so
-  // no fused evaluation + partition pass (as COBALT_EVAL_PART=0)
-  const bool mono = c->mono_on;
+  // monotone / interaction constraints: one GPU, and the constrained evaluation is a kernel of its own
+  // (k_eval_mono), so no fused evaluation + partition pass (as COBALT_EVAL_PART=0)
+  const bool mono = c->mono_on || c->inter_on;
   if (mono && (dp || sampled)) return -16;
   const bool eval_part = !mono && env_ep != 0 && (!ipc_fused || eb_ok) && eval_fg == 0 && ep_steps <= 8 && d.F <= 32;
   // A level's fused pass: {item rows (0: separate k_eval + k_partition), mode}. Every-block form: the
@@ -3747,7 +3809,7 @@ static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool s
         const int ng = ceil_div(d.F, eval_fg);
         const dim3 eg(1 << level, ng), eb(ceil_div(eval_fg, 2) * kWave);
         if (mono)
-          GLAUNCH("k_eval", (k_eval_mono<true>), eg, eb, 0, stream, d, level, parity, t, eval_fg, EvalSlots{}, c->mono);
+          CONS_EVAL(true, eg, eb, 0, stream, d, level, parity, t, eval_fg, EvalSlots{}, c->cons);
         else if (d.ipc_epoch)
           GLAUNCH("k_eval", (k_eval<true, true, true>), eg, eb, fused_lds, stream, d, level, parity, t, eval_fg, EvalSlots{});
         else if (dp)
@@ -3755,16 +3817,14 @@ static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool s
         else
           GLAUNCH("k_eval", (k_eval<true, false, false>), eg, eb, 0, stream, d, level, parity, t, eval_fg, EvalSlots{});
         if (mono)
-          GLAUNCH("k_eval_finish", k_eval_finish_mono, dim3(1 << level), dim3(kWave), 0, stream, d, level, parity, ng,
-                  c->mono);
+          CONS_FINISH(dim3(1 << level), dim3(kWave), 0, stream, d, level, parity, ng, c->cons);
         else if (dp)
           GLAUNCH("k_eval_finish", k_eval_finish<true>, dim3(1 << level), dim3(kWave), 0, stream, d, level, parity, ng);
         else
           GLAUNCH("k_eval_finish", k_eval_finish<false>, dim3(1 << level), dim3(kWave), 0, stream, d, level, parity, ng);
       } else {
         if (mono)
-          GLAUNCH("k_eval", (k_eval_mono<false>), dim3(1 << level), dim3(1024), 0, stream, d, level, parity, t, d.F,
-                  c->eval_slots, c->mono);
+          CONS_EVAL(false, dim3(1 << level), dim3(1024), 0, stream, d, level, parity, t, d.F, c->eval_slots, c->cons);
         else if (d.ipc_epoch)
           GLAUNCH("k_eval", (k_eval<false, true, true>), dim3(1 << level), dim3(1024), fused_lds, stream, d, level, parity,
                   t, d.F, c->eval_slots);
@@ -4172,14 +4232,40 @@ COBALT_API int cobalt_gbdt_set_monotone(void* h, const int8_t* cons, int n_feat)
   c->mono_on = false;
   if (!any) return 0;
   if (c->cfg.comm) return -16;
-  if (!c->mono.c) {
+  MonoDev& m = c->cons.mono;
+  if (!m.c) {
     int rc;
-    if ((rc = dev_alloc(c, (void**)&c->mono.c, (size_t)n_feat))) return rc;
-    if ((rc = dev_alloc(c, (void**)&c->mono.bounds, (size_t)c->max_nodes * 2 * sizeof(double)))) return rc;
+    if ((rc = dev_alloc(c, (void**)&m.c, (size_t)n_feat))) return rc;
+    if ((rc = dev_alloc(c, (void**)&m.bounds, (size_t)c->max_nodes * 2 * sizeof(double)))) return rc;
   }
   // (blocking copy: no kernel of this context is in flight between two fits, and every later grow call sees it)
-  CK(hipMemcpy(const_cast<int8_t*>(c->mono.c), cons, (size_t)n_feat, hipMemcpyHostToDevice));
+  CK(hipMemcpy(const_cast<int8_t*>(m.c), cons, (size_t)n_feat, hipMemcpyHostToDevice));
   c->mono_on = true;
+  return 0;
+}
+
+// Interaction constraints of this fit (after create / reuse, before the first grow call): `fgroups` = n_feat
+// host words, bit k of word f set iff feature f is in group k (n_groups <= 64 groups; a feature in no group
+// has word 0). n_groups == 0 (or a null pointer) leaves the fit unconstrained; any group, even one holding
+// every feature, runs the constrained kernels. One GPU, in core, as the monotone constraints (with which they
+// combine); cobalt_gbdt_reuse clears the state for the next fit.
+COBALT_API int cobalt_gbdt_set_interaction(void* h, const uint64_t* fgroups, int n_feat, int n_groups) {
+  GbdtCtx* c = static_cast<GbdtCtx*>(h);
+  if (!c || n_feat != c->d.F || n_groups < 0 || n_groups > 64) return -13;
+  c->inter_on = false;
+  if (!fgroups || n_groups == 0) return 0;
+  const uint64_t used = n_groups == 64 ? ~0ull : (1ull << n_groups) - 1;
+  for (int f = 0; f < n_feat; ++f)
+    if (fgroups[f] & ~used) return -13;
+  if (c->cfg.comm) return -16;
+  InterDev& it = c->cons.inter;
+  if (!it.fgroups) {
+    int rc;
+    if ((rc = dev_alloc(c, (void**)&it.fgroups, (size_t)n_feat * sizeof(uint64_t)))) return rc;
+    if ((rc = dev_alloc(c, (void**)&it.compat, (size_t)c->max_nodes * sizeof(uint64_t)))) return rc;
+  }
+  CK(hipMemcpy(const_cast<uint64_t*>(it.fgroups), fgroups, (size_t)n_feat * sizeof(uint64_t), hipMemcpyHostToDevice));
+  c->inter_on = true;
   return 0;
 }
 
@@ -4249,6 +4335,7 @@ COBALT_API int cobalt_gbdt_reuse(void* h, const GbdtConfig* cfg) {
   c->fit_first = 0;
   c->fault_tree = -1;
   c->mono_on = false;  // (the next fit sets its own constraints, if any)
+  c->inter_on = false;
   if (c->err_pinned) memset(c->err_pinned, 0, 64);
   return 0;
 }

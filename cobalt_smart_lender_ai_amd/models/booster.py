@@ -143,6 +143,13 @@ class Booster:
         v = self.train_params.get("monotone_constraints")
         return tuple(int(c) for c in v) if v else None
 
+    @property
+    def interaction_constraints(self) -> list[list[int]] | None:
+        """The interaction constraints the model was fitted under: the feature groups as sorted index lists
+        (None: unconstrained)."""
+        v = self.train_params.get("interaction_constraints")
+        return [[int(i) for i in g] for g in v] if v else None
+
     def slice(self, n_trees: int) -> "Booster":
         return Booster(self.trees[:n_trees], self.feature_names, self.feature_types, self.base_score,
                        self.num_feature, self.objective, dict(self.train_params), dict(self.attributes))
@@ -267,6 +274,7 @@ class Booster:
         p.update({k: v for k, v in self.train_params.items() if v is not None})
         f = _fmt_float
         mono = self.monotone_constraints
+        inter = self.interaction_constraints
         return {
             "learner": {
                 "generic_param": {"device": "cpu", "fail_on_invalid_gpu_id": "0", "n_jobs": "0", "nthread": "0",
@@ -282,7 +290,8 @@ class Booster:
                     "tree_train_param": {
                         "alpha": f(p["reg_alpha"]), "cache_opt": "1", "colsample_bylevel": "1",
                         "colsample_bynode": "1", "colsample_bytree": f(p["colsample_bytree"]), "eta": f(p["eta"]),
-                        "gamma": f(p["gamma"]), "grow_policy": "depthwise", "interaction_constraints": "",
+                        "gamma": f(p["gamma"]), "grow_policy": "depthwise",
+                        "interaction_constraints": json.dumps(inter) if inter else "",
                         "lambda": f(p["reg_lambda"]), "learning_rate": f(p["eta"]), "max_bin": str(int(p["max_bin"])),
                         "max_cat_threshold": "64", "max_cat_to_onehot": "4", "max_delta_step": "0",
                         "max_depth": str(int(p["max_depth"])), "max_leaves": "0",
@@ -364,6 +373,9 @@ class Booster:
         mono = parse_monotone_string(ttp.get("monotone_constraints", "()"))
         if any(mono):
             params["monotone_constraints"] = mono
+        inter = parse_interaction_string(ttp.get("interaction_constraints", ""))
+        if inter:
+            params["interaction_constraints"] = inter
         spw = lrn.get("objective", {}).get("reg_loss_param", {}).get("scale_pos_weight")
         if spw is not None:
             params["scale_pos_weight"] = float(spw)
@@ -422,6 +434,18 @@ def parse_monotone_string(s: str) -> tuple[int, ...]:
         return tuple(int(tok) for tok in body.split(",") if tok.strip())
     except ValueError:
         raise ValueError(f"monotone_constraints: cannot parse {s!r} (expected a form like '(1,0,-1)')") from None
+
+
+def parse_interaction_string(s: str) -> list[list[int]]:
+    """XGBoost's ``interaction_constraints`` config string ``"[[0, 1], [2, 3]]"`` -> index groups; ``""`` /
+    ``"[]"`` -> ``[]``."""
+    if not s or not s.strip():
+        return []
+    try:
+        return [[int(i) for i in g] for g in json.loads(s)]
+    except (ValueError, TypeError):
+        raise ValueError(f"interaction_constraints: cannot parse {s!r} (expected a form like "
+                         "'[[0, 1], [2, 3]]')") from None
 
 
 def _jsonable(v: Any) -> Any:

@@ -35,7 +35,7 @@ import torch
 from . import gbdt_host, sketch
 from .booster import NODE_DTYPE, Booster, trees_from_heap_nodes
 from . import gbdt
-from .gbdt import GBDTParams, _refuse_monotone, _resolve_device, feature_masks
+from .gbdt import GBDTParams, _refuse_interaction, _refuse_monotone, _resolve_device, feature_masks
 from .stream import ChunkSource, _as_np, _PinnedUploader, stream_cuts
 
 OOC_BINS = 2048
@@ -139,6 +139,7 @@ def train_external(source: ChunkSource, params: GBDTParams | dict | None = None,
     elif isinstance(params, dict):
         params = GBDTParams.from_kwargs(**params)
     _refuse_monotone(params, "in out-of-core training (train_external)")
+    _refuse_interaction(params, "in out-of-core training (train_external)")
     if not 0.0 < sample_rate <= 1.0:
         raise ValueError("sample_rate must be in (0, 1]")
     if int(params.grad_bits) != 17:

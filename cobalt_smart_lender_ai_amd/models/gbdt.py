@@ -74,6 +74,11 @@ class GBDTParams:
     # string form "(1,0,-1)", or {feature_name: +-1} (resolved against the fit's feature names; unnamed
     # features get 0). None / () / "()" / all zeros: the unconstrained fit. See :func:`resolve_monotone`.
     monotone_constraints: Any = None
+    # interaction constraints (XGBoost's ``interaction_constraints``): a list of feature groups, as lists of
+    # indices, lists of feature names (resolved against the fit's feature names) or the string / JSON form
+    # "[[0, 1], [2, 3]]". Features may share a root-to-leaf path only when one group holds them all.
+    # None / [] / "" / "[]": the unconstrained fit. See :func:`resolve_interaction`.
+    interaction_constraints: Any = None
 
     @classmethod
     def from_kwargs(cls, **kw) -> "GBDTParams":
@@ -352,11 +357,13 @@ def subset_features(bd: BinnedData, feats) -> BinnedData:
 
 
 def expand_features(bst: Booster, feats, n_features: int, feature_names: Sequence[str] | None = None,
-                    feature_types: Sequence[str] | None = None, monotone_constraints=None) -> Booster:
+                    feature_types: Sequence[str] | None = None, monotone_constraints=None,
+                    interaction_constraints=None) -> Booster:
     """A booster fitted on :func:`subset_features` columns, re-expressed over the full feature space
     (split indices mapped back; leaves keep index 0 as XGBoost writes them). Its monotone constraints go
     back to full width: ``monotone_constraints`` (the full vector) when given, else the subset's entries
-    at ``feats`` and 0 elsewhere."""
+    at ``feats`` and 0 elsewhere. Likewise its interaction constraints: ``interaction_constraints`` (the
+    full-width groups) when given, else the subset's groups with their indices mapped back."""
     from .booster import Tree
 
     f = np.asarray(feats, dtype=np.int32)
@@ -372,6 +379,10 @@ def expand_features(bst: Booster, feats, n_features: int, feature_names: Sequenc
         full = np.zeros(int(n_features), dtype=np.int8)
         full[f] = bst.monotone_constraints
         tparams["monotone_constraints"] = tuple(int(c) for c in full)
+    if interaction_constraints is not None:
+        tparams["interaction_constraints"] = [[int(i) for i in g] for g in interaction_constraints]
+    elif bst.interaction_constraints is not None:
+        tparams["interaction_constraints"] = [[int(f[i]) for i in g] for g in bst.interaction_constraints]
     return Booster(trees, list(feature_names) if feature_names is not None else None,
                    list(feature_types) if feature_types is not None else None, bst.base_score, int(n_features),
                    bst.objective, tparams, dict(bst.attributes))
@@ -427,6 +438,92 @@ def _mono_plain(mc) -> list | None:
     if isinstance(mc, str):
         return list(parse_monotone_string(mc))
     return list(np.asarray(mc).reshape(-1).tolist())
+
+
+GPU_MAX_INTERACTION_GROUPS = 64  # one bit per group in the device's 64-bit group words (csrc/gbdt.hip InterDev)
+
+
+def _inter_plain(ic) -> list:
+    """``interaction_constraints`` as a list of lists of raw entries (the string form parsed as JSON)."""
+    if ic is None:
+        return []
+    if isinstance(ic, str):
+        if not ic.strip():
+            return []
+        try:
+            ic = json.loads(ic)
+        except ValueError:
+            raise ValueError(f"interaction_constraints: cannot parse {ic!r} (expected a form like "
+                             "'[[0, 1], [2, 3]]')") from None
+    if isinstance(ic, (dict, str, bytes)) or not hasattr(ic, "__iter__"):
+        raise ValueError("interaction_constraints must be a list of lists of feature indices or names")
+    groups = []
+    for g in ic:
+        if isinstance(g, (dict, str, bytes)) or not hasattr(g, "__iter__"):
+            raise ValueError(f"interaction_constraints: every group is a list of features (got {g!r})")
+        groups.append(list(g))
+    return groups
+
+
+def resolve_interaction(ic, n_features: int, feature_names: Sequence[str] | None = None, *,
+                        max_groups: int | None = None) -> list[list[int]] | None:
+    """``interaction_constraints`` in any accepted form (a list of lists of feature indices or of feature
+    names, XGBoost's string / JSON form ``"[[0, 1], [2, 3]]"``) -> the canonical groups: index lists, each
+    sorted and without duplicates, empty groups dropped; None for an unconstrained fit (None, ``[]``, ``""``,
+    ``"[]"``, only empty groups). A non-empty constraint is never simplified away: one group holding every
+    feature stays a constraint. ``ValueError``: an index out of range, an entry that is neither an integer
+    nor a name (bools and floats included), a name without feature names or an unknown one, more than
+    ``max_groups`` groups (the GPU trainer's 64)."""
+    names = [str(n) for n in feature_names] if feature_names is not None else None
+    out = []
+    for g in _inter_plain(ic):
+        idx = set()
+        for e in g:
+            if isinstance(e, str):
+                if names is None:
+                    raise ValueError(f"interaction_constraints given by feature name ({e!r}) needs feature_names")
+                if e not in names:
+                    raise ValueError(f"interaction_constraints names an unknown feature: {e!r}")
+                idx.add(names.index(e))
+            elif isinstance(e, (bool, np.bool_)) or not isinstance(e, (int, np.integer)):
+                raise ValueError(f"interaction_constraints entries must be feature indices or names (got {e!r})")
+            elif not 0 <= int(e) < n_features:
+                raise ValueError(f"interaction_constraints index {int(e)} is out of range for {n_features} features")
+            else:
+                idx.add(int(e))
+        if idx:
+            out.append(sorted(idx))
+    if not out:
+        return None
+    if max_groups is not None and len(out) > max_groups:
+        raise ValueError(f"interaction_constraints has {len(out)} groups; the GPU trainer supports at most "
+                         f"{max_groups} (fit on the CPU for more)")
+    return out
+
+
+def _refuse_interaction(params: "GBDTParams", what: str) -> None:
+    """As :func:`_refuse_monotone`: every trainer but the in-core, one-device one refuses the argument by name."""
+    if any(len(g) for g in _inter_plain(getattr(params, "interaction_constraints", None))):
+        raise ValueError(f"interaction_constraints is not supported {what}")
+
+
+def subset_interaction(groups: list[list[int]] | None, feats) -> list[list[int]] | None:
+    """Full-width groups restricted to the surviving features ``feats`` (ascending full-width indices) and
+    renumbered to their positions. Groups that become empty are dropped; a group that shrinks to one
+    feature stays (a singleton is not the same as ungrouped). None when no group survives."""
+    if groups is None:
+        return None
+    pos = {int(f): i for i, f in enumerate(np.asarray(feats).reshape(-1).tolist())}
+    out = [sorted(pos[f] for f in g if f in pos) for g in groups]
+    return [g for g in out if g] or None
+
+
+def interaction_words(groups: list[list[int]], n_features: int) -> np.ndarray:
+    """The device's form of the groups: uint64 [n_features], bit k of word f set iff f is in group k."""
+    w = np.zeros(int(n_features), dtype=np.uint64)
+    for k, g in enumerate(groups):
+        w[np.asarray(g, dtype=np.int64)] |= np.uint64(1) << np.uint64(k)
+    return w
 
 
 def check_grad_bits(grad_bits: int, n_features: int, device_type: str) -> None:
@@ -580,6 +677,7 @@ def train(X, y, params: GBDTParams | dict | None = None, *, sample_weight=None, 
     t0 = time.perf_counter()
     if dist is not None:
         _refuse_monotone(params, "in data-parallel fits (dist)")
+        _refuse_interaction(params, "in data-parallel fits (dist)")
     evals = _eval_monitor(evals, eval_metric, early_stopping_rounds, _resolve_device(device, X), int(X.shape[1]),
                           dist, checkpoint_path is not None, verbose_eval)
     ckpt = Checkpointer(checkpoint_path, checkpoint_every, params, dist) if checkpoint_path else None
@@ -595,6 +693,10 @@ def train(X, y, params: GBDTParams | dict | None = None, *, sample_weight=None, 
     check_grad_bits(int(params.grad_bits), int(X.shape[1]), dev.type)
     if dev.type == "cuda":
         check_gpu_shape(int(params.max_depth), int(X.shape[0]))
+    # (the constraint's form and the GPU's group limit too: a refusal comes before any device work)
+    resolve_interaction(params.interaction_constraints, int(X.shape[1]), feature_names if feature_names is not None
+                        else (init_booster.feature_names if init_booster is not None else None),
+                        max_groups=GPU_MAX_INTERACTION_GROUPS if dev.type == "cuda" else None)
     init_margin = None
     if init_booster is not None:
         from ..ops import predict_ops
@@ -645,8 +747,12 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
     N, F = bd.n_rows, bd.n_features
     if dist is not None:
         _refuse_monotone(params, "in data-parallel fits (dist)")
+        _refuse_interaction(params, "in data-parallel fits (dist)")
     mono = resolve_monotone(params.monotone_constraints, F, feature_names if feature_names is not None else (
         init_booster.feature_names if init_booster is not None else None))
+    inter = resolve_interaction(params.interaction_constraints, F, feature_names if feature_names is not None else (
+        init_booster.feature_names if init_booster is not None else None),
+        max_groups=GPU_MAX_INTERACTION_GROUPS if dev.type == "cuda" else None)
     check_grad_bits(grad_bits, F, dev.type)
     if dev.type == "cuda":
         check_gpu_shape(int(params.max_depth), N)
@@ -731,7 +837,9 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
                                          colsample_bytree=float(params.colsample_bytree),
                                          max_bin=int(params.max_bin), scale_pos_weight=spw, seed=hp.seed,
                                          **({"monotone_constraints": tuple(int(c) for c in mono)}
-                                            if mono is not None else {})))
+                                            if mono is not None else {}),
+                                         **({"interaction_constraints": [list(g) for g in inter]}
+                                            if inter is not None else {})))
 
     def early_stop(s0: int) -> bool:
         """Early stopping: score the segment's trees (rounds s0 ...); on a stop keep trees 0..that round."""
@@ -761,7 +869,8 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
                                   gamma=float(params.gamma), min_child_weight=float(params.min_child_weight),
                                   subsample=float(params.subsample), seed=int(params.random_state),
                                   gscale=1.0 if exact_fp64 else gscale, hscale=1.0 if exact_fp64 else hscale,
-                                  quant=not exact_fp64, qbits=grad_bits, monotone=mono)
+                                  quant=not exact_fp64, qbits=grad_bits, monotone=mono,
+                                  interaction=inter)
     if exact_fp64 and dev.type != "cpu":
         raise ValueError("exact_fp64 is the host (CPU) reference trainer")
     tp = rep.mark("labels_weights", tp, dev)
@@ -791,6 +900,8 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
             tr.set_binary_labels(float(np.float32(spw)))
         if mono is not None:  # (a reused context starts every fit unconstrained: cobalt_gbdt_reuse)
             tr.set_monotone(mono)
+        if inter is not None:
+            tr.set_interaction(interaction_words(inter, F), len(inter))
         tp = rep.mark("trainer_setup", tp, dev)
         completed = False
         try:
@@ -964,6 +1075,9 @@ class Checkpointer:
             plain = _mono_plain(mc)
             mc = [int(v) for v in plain] if any(plain) else None
         meta["params"]["monotone_constraints"] = mc
+        # (likewise: the groups as given -- indices or names --, None without constraints)
+        ic = [[e if isinstance(e, str) else int(e) for e in g] for g in _inter_plain(self.params.interaction_constraints)]
+        meta["params"]["interaction_constraints"] = [g for g in ic if g] or None
         return meta
 
     def save(self, booster: Booster) -> None:
@@ -1015,13 +1129,15 @@ class GBDTClassifier:
     _param_names = ["n_estimators", "max_depth", "learning_rate", "gamma", "min_child_weight", "reg_lambda",
                     "reg_alpha", "subsample", "colsample_bytree", "max_bin", "scale_pos_weight", "random_state",
                     "base_score", "eval_metric", "use_label_encoder", "device", "importance_type", "n_jobs",
-                    "sketch_rows", "sketch_weight", "early_stopping_rounds", "monotone_constraints"]
+                    "sketch_rows", "sketch_weight", "early_stopping_rounds", "monotone_constraints",
+                    "interaction_constraints"]
 
     def __init__(self, n_estimators=None, max_depth=None, learning_rate=None, gamma=None, min_child_weight=None,
                  reg_lambda=None, reg_alpha=None, subsample=None, colsample_bytree=None, max_bin=None,
                  scale_pos_weight=None, random_state=None, base_score=None, eval_metric=None,
                  use_label_encoder=None, device=None, importance_type=None, n_jobs=None, sketch_rows=None,
-                 sketch_weight=None, early_stopping_rounds=None, monotone_constraints=None):
+                 sketch_weight=None, early_stopping_rounds=None, monotone_constraints=None,
+                 interaction_constraints=None):
         self.n_estimators = n_estimators
         self.max_depth = max_depth
         self.learning_rate = learning_rate
@@ -1044,13 +1160,15 @@ class GBDTClassifier:
         self.sketch_weight = sketch_weight
         self.early_stopping_rounds = early_stopping_rounds
         self.monotone_constraints = monotone_constraints
+        self.interaction_constraints = interaction_constraints
 
     # sklearn protocol
     def get_params(self, deep: bool = True) -> dict[str, Any]:
-        # ``monotone_constraints`` is listed when it is set (``clone`` / ``set_params`` carry it); an estimator
-        # without constraints reports exactly the parameters it reported before the argument existed
+        # ``monotone_constraints`` / ``interaction_constraints`` are listed when set (``clone`` / ``set_params``
+        # carry them); an estimator without constraints reports exactly the parameters it reported before the
+        # arguments existed
         return {k: getattr(self, k) for k in self._param_names
-                if k != "monotone_constraints" or self.monotone_constraints is not None}
+                if k not in ("monotone_constraints", "interaction_constraints") or getattr(self, k) is not None}
 
     def set_params(self, **params) -> "GBDTClassifier":
         for k, v in params.items():
@@ -1208,7 +1326,11 @@ class GBDTClassifier:
                                            "reg_alpha", "reg_lambda", "subsample", "colsample_bytree",
                                            "scale_pos_weight", "base_score", "random_state", "max_bin", "device",
                                            "importance_type", "n_jobs", "eval_metric", "early_stopping_rounds",
-                                           "monotone_constraints"]}
+                                           "monotone_constraints", "interaction_constraints"]}
+        ic = p["interaction_constraints"]
+        if ic is not None and not isinstance(ic, str):  # lists are written in XGBoost's string (JSON) form
+            p["interaction_constraints"] = json.dumps(
+                [[e if isinstance(e, str) else int(e) for e in g] for g in _inter_plain(ic)])
         mc = p["monotone_constraints"]
         if mc is not None and not isinstance(mc, (str, dict)):  # a sequence is written in XGBoost's string form
             from .booster import monotone_string

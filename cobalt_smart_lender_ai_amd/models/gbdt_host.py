@@ -88,6 +88,10 @@ class HostGbdtParams:
     # monotone constraints: int8 [F] in {-1, 0, +1} (None: unconstrained). Constrained mode: every node
     # carries fp64 weight bounds [lo, hi] (root: -inf, +inf), see _eval_node_mono / grow_tree_host
     monotone: np.ndarray | None = None
+    # interaction constraints: the resolved groups (lists of feature indices; None: unconstrained, any
+    # number of groups). Below the root a node evaluates the features of the groups that hold every
+    # feature split on along its path, see grow_tree_host
+    interaction: list | None = None
 
 
 def quant_scales(w_max: float, bits: int = QBITS) -> tuple[float, float]:
@@ -311,6 +315,12 @@ def grow_tree_host(bins: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, gq: np
     mono = p.monotone is not None
     bounds = np.empty((max_nodes, 2), dtype=np.float64)  # monotone constraints: node weight bounds [lo, hi]
     bounds[:, 0], bounds[:, 1] = -np.inf, np.inf
+    # interaction constraints: a node's path features and its allowed set (the root: every feature)
+    inter = p.interaction is not None
+    groups = [frozenset(int(f) for f in g) for g in p.interaction] if inter else []
+    fm = np.asarray(fmask).astype(bool)
+    path: dict[int, frozenset] = {0: frozenset()}
+    allowed: dict[int, np.ndarray] = {0: np.ones(F, dtype=bool)}
     rows: dict[int, np.ndarray] = {0: np.arange(N, dtype=np.int64)}
     hist_prev: dict[int, np.ndarray] = {}
     for level in range(D + 1):
@@ -353,7 +363,8 @@ def grow_tree_host(bins: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, gq: np
                 continue
             G, H = GH[n, 0].item(), GH[n, 1].item()
             if level < D:
-                best, Gd, Hd = _eval_node(hist_cur[n], G, H, nbins, fmask, p, bounds[n, 0], bounds[n, 1])
+                best, Gd, Hd = _eval_node(hist_cur[n], G, H, nbins, fm & allowed[n] if inter else fmask, p,
+                                          bounds[n, 0], bounds[n, 1])
             else:
                 best, Gd, Hd = None, G * (1.0 / p.gscale), H * (1.0 / p.hscale)
             wgt = _calc_weight(Gd, Hd, p.reg_lambda, p.reg_alpha, p.min_child_weight)
@@ -391,6 +402,13 @@ def grow_tree_host(bins: np.ndarray, cuts: np.ndarray, nbins: np.ndarray, gq: np
                     c = int(p.monotone[f])
                     bounds[L] = (lo, mid) if c > 0 else ((mid, hi) if c < 0 else (lo, hi))
                     bounds[R] = (mid, hi) if c > 0 else ((lo, mid) if c < 0 else (lo, hi))
+                if inter:  # the children may use the features of the groups that hold the whole path
+                    path[L] = path[R] = path[n] | {int(f)}
+                    al = np.zeros(F, dtype=bool)
+                    for g in groups:
+                        if path[L] <= g:
+                            al[list(g)] = True
+                    allowed[L] = allowed[R] = al
                 b = bins[r, f]
                 go_left = np.where(b == 255, dl == 1, b.astype(np.int64) <= j)
                 rows[L] = r[go_left]

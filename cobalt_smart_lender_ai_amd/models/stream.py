@@ -24,7 +24,8 @@ import numpy as np
 import torch
 
 from . import sketch
-from .gbdt import SKETCH_AUTO, SKETCH_SAMPLE_ROWS, BinnedData, GBDTParams, _refuse_monotone, _resolve_device, train_binned
+from .gbdt import (SKETCH_AUTO, SKETCH_SAMPLE_ROWS, BinnedData, GBDTParams, _refuse_interaction, _refuse_monotone,
+                   _resolve_device, train_binned)
 
 Chunk = tuple  # (X [n, F] float32, y [n])
 ChunkSource = Callable[[], Iterable[Chunk]]
@@ -198,6 +199,7 @@ def train_stream(source: ChunkSource, params: GBDTParams | dict | None = None, *
     elif isinstance(params, dict):
         params = GBDTParams.from_kwargs(**params)
     _refuse_monotone(params, "in stream training (train_stream)")
+    _refuse_interaction(params, "in stream training (train_stream)")
     bd, y = bin_stream(source, n_rows=n_rows, max_bin=params.max_bin, sketch_rows=params.sketch_rows,
                        device=device, dist=dist, row_offset=row_offset, n_rows_global=n_rows_global)
     return train_binned(bd, y, params, dist=dist, **kw)

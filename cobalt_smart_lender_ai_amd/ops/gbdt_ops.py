@@ -220,6 +220,16 @@ class GpuGbdtTrainer:
             raise ValueError("monotone_constraints is not supported in data-parallel fits")
         _native.check(rc, "cobalt_gbdt_set_monotone")
 
+    def set_interaction(self, fgroups: np.ndarray, n_groups: int) -> None:
+        """Interaction constraints of this fit, before the first :meth:`grow`: uint64 [n_feat], bit k of
+        word f set iff feature f is in group k (``n_groups`` <= 64). One GPU; combines with
+        :meth:`set_monotone`; a context taken from the cache starts unconstrained."""
+        w = np.ascontiguousarray(fgroups, dtype=np.uint64)
+        rc = self.lib.cobalt_gbdt_set_interaction(self.h, w.ctypes.data, int(w.shape[0]), int(n_groups))
+        if rc == -16:
+            raise ValueError("interaction_constraints is not supported in data-parallel fits")
+        _native.check(rc, "cobalt_gbdt_set_interaction")
+
     def plan(self) -> dict:
         """The last grow call's launch plan (csrc/gbdt.hip cobalt_gbdt_plan)."""
         fn = getattr(self.lib, "cobalt_gbdt_plan", None)

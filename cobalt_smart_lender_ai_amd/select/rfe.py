@@ -61,16 +61,23 @@ def rfe(X, y, params: gbdt.GBDTParams | dict, n_features_to_select: int = 20, st
     # monotone constraints, resolved once over the full width (a dict may name a feature that a later
     # step eliminates); a repacked fit takes the survivors' entries
     mono = gbdt.resolve_monotone(params.monotone_constraints, F, feature_names)
+    # interaction constraints likewise: a repacked fit takes each group's surviving features, renumbered
+    inter = gbdt.resolve_interaction(params.interaction_constraints, F, feature_names)
 
     def fit(sup: np.ndarray):
         feats = np.nonzero(sup)[0]
-        if not repack or len(feats) == F:
+        sub_inter = gbdt.subset_interaction(inter, feats)
+        # (no group survives: the survivors are all ungrouped, which no constraint on the subset expresses)
+        if not repack or len(feats) == F or (inter is not None and sub_inter is None):
             return gbdt.train_binned(bd, yt, params, feature_mask=sup, feature_names=feature_names)
         sub = gbdt.subset_features(bd, feats)
         names = [feature_names[i] for i in feats] if feature_names is not None else None
         sub_params = params if mono is None else replace(params, monotone_constraints=tuple(int(c) for c in mono[feats]))
+        if inter is not None:
+            sub_params = replace(sub_params, interaction_constraints=sub_inter)
         b = gbdt.train_binned(sub, yt, sub_params, feature_names=names)
-        return gbdt.expand_features(b, feats, F, feature_names, monotone_constraints=mono)
+        return gbdt.expand_features(b, feats, F, feature_names, monotone_constraints=mono,
+                                    interaction_constraints=inter)
 
     while support.sum() > n_features_to_select:
         feats = np.nonzero(support)[0]
