@@ -204,7 +204,7 @@ __global__ __launch_bounds__(kShapChunk) void k_treeshap(const float* __restrict
       if (l <= k) {
         const PathElem e = elems[e0 + l - 1];
         const float v = x[e.feat];
-        const double one = (v != v) ? (e.nan_ok ? 1.0 : 0.0) : ((v >= e.lo && v < e.hi) ? 1.0 : 0.0);
+        const double one = (v != v) ? (e.nan_ok ? 1.0 : 0.0) : ((v >= e.lo && !(v >= e.hi)) ? 1.0 : 0.0);
         z[l] = e.zero; o[l] = one; feat[l] = e.feat;
         w[l] = 0.0;
 #pragma unroll
@@ -234,7 +234,7 @@ __global__ __launch_bounds__(kShapChunk) void k_treeshap(const float* __restrict
             }
           }
         } else {
-          const double iz = 1.0 / zero;
+          const double iz = zero != 0.0 ? 1.0 / zero : 0.0;  // zero-cover branch: every w[j] is 0, the term is 0
 #pragma unroll
           for (int j = P - 2; j >= 0; --j) {
             if (j <= k - 1) total += w[j] * (iz * kShapInv[k - j]);
@@ -306,7 +306,7 @@ __global__ void k_shap_table(const PathElem* __restrict__ elems, const int32_t* 
             }
           }
         } else {
-          const double iz = 1.0 / zero;
+          const double iz = zero != 0.0 ? 1.0 / zero : 0.0;  // zero-cover branch: every w[j] is 0, the term is 0
 #pragma unroll
           for (int j = P - 2; j >= 0; --j) {
             if (j <= k - 1) total += w[j] * (iz * kShapInv[k - j]);
@@ -336,7 +336,7 @@ __device__ __forceinline__ int shap_pattern(const PathElem* __restrict__ el, int
     if (l < k) {
       const PathElem e = el[l];
       const float v = x[e.feat];
-      const bool one = (v != v) ? (e.nan_ok != 0) : (v >= e.lo && v < e.hi);
+      const bool one = (v != v) ? (e.nan_ok != 0) : (v >= e.lo && !(v >= e.hi));
       pat |= (int)one << l;
       fe[l] = e.feat;
     }

@@ -5,7 +5,8 @@
 #include "common.h"
 
 struct PathElem {
-  float lo, hi;        // row follows the path on this feature iff lo <= x < hi (non-missing)
+  float lo, hi;        // row follows the path on this feature iff x >= lo && !(x >= hi) (non-missing);
+                       // no upper bound: hi = NaN (+inf would turn x = +inf away), no lower bound: lo = -inf
   int32_t feat;        // feature index
   int32_t nan_ok;      // row with NaN follows the path on this feature
   double zero;         // product of cover(child)/cover(parent) over the merged occurrences

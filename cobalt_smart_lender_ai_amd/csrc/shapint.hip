@@ -152,7 +152,7 @@ __global__ __launch_bounds__(R) void k_shap_interactions(const float* __restrict
           const PathElem e = elems[e0 + l - 1];
           if ((unsigned)e.feat < (unsigned)F) {
             const float v = s_x[e.feat];
-            o[l] = (v != v) ? (e.nan_ok ? 1.0 : 0.0) : ((v >= e.lo && v < e.hi) ? 1.0 : 0.0);
+            o[l] = (v != v) ? (e.nan_ok ? 1.0 : 0.0) : ((v >= e.lo && !(v >= e.hi)) ? 1.0 : 0.0);
             s_pos[(size_t)tid * fs + e.feat] = (uint8_t)(l - 1);
           }
           z[l] = e.zero;
@@ -249,7 +249,8 @@ COBALT_API int cobalt_treeshap_interactions(const float* X, int64_t n, int F, in
   if (max_len + 1 > kMaxPath) return -3;
   if (n > 0x7FFFFFFF) return -4;
   if (n_paths < 0 || ldx < F) return -6;
-  if (!X || !phi || !out || (n_paths > 0 && (!elems || !path_ptr || !path_val))) return -6;
+  // (a forest of single-leaf trees has paths and no element: max_len 0, elems is never read)
+  if (!X || !phi || !out || (n_paths > 0 && (!path_ptr || !path_val)) || (max_len > 0 && !elems)) return -6;
   const PathElem* pe = static_cast<const PathElem*>(elems);
   if (max_len + 1 <= 8)
     return shapint_launch<8, 256, true>(X, n, F, ldx, pe, path_ptr, path_val, n_paths, phi, out, stream);

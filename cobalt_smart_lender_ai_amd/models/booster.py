@@ -681,6 +681,10 @@ def _treeshap_row(t: Tree, cov, val, x, phi) -> None:
         return total * (l + 1)
 
     def recurse(j, m, pz, po, pi):
+        if pz == 0 and po == 0:
+            # a zero-cover branch the row does not take: every subset weight below it has the factor
+            # pz or po, so it contributes exactly 0 (UNWIND would divide by pz)
+            return
         m = extend(m, pz, po, pi)
         if t.left_children[j] == -1:
             feats, zs, os_, ws = m
@@ -723,7 +727,8 @@ def iter_leaf_paths(t: Tree) -> Iterable[tuple[int, list[tuple[int, int, bool]]]
 
 def merged_leaf_paths(t: Tree) -> Iterable[tuple[float, list[tuple[int, np.float32, np.float32, bool, float]]]]:
     """Yield (leaf value, [(feature, lo, hi, nan_ok, zero fraction)]) per leaf path with the splits on
-    one feature merged into one element: a row follows the element iff ``lo <= x < hi`` (NaN: iff
+    one feature merged into one element: a row follows the element iff ``x >= lo and not x >= hi``
+    (``hi`` is NaN when no split bounds the feature from above, so ``x = +inf`` follows; NaN rows: iff
     every merged split sends missing values this way); the zero fraction is the product of the
     cover ratios of the merged splits. Elements are in order of first occurrence."""
     cov = t.sum_hessian.astype(np.float64)
@@ -731,10 +736,10 @@ def merged_leaf_paths(t: Tree) -> Iterable[tuple[float, list[tuple[int, np.float
         merged: dict[int, list] = {}
         for node, f, went_left in path:
             child = int(t.left_children[node] if went_left else t.right_children[node])
-            m = merged.setdefault(f, [np.float32(-np.inf), np.float32(np.inf), True, 1.0])
+            m = merged.setdefault(f, [np.float32(-np.inf), np.float32(np.nan), True, 1.0])
             thr = t.split_conditions[node]
             if went_left:
-                m[1] = min(m[1], thr)
+                m[1] = thr if np.isnan(m[1]) else min(m[1], thr)
             else:
                 m[0] = max(m[0], thr)
             m[2] = m[2] and (bool(t.default_left[node]) == went_left)
@@ -794,7 +799,7 @@ def treeshap_interactions_host(b: Booster, X: np.ndarray) -> np.ndarray:
     rows = np.arange(N)[:, None]
     for k, (v, feat, lo, hi, nan_ok, zero) in _paths_by_length(b):
         xv = X[:, feat]                                                             # [N, P, k]
-        one = np.where(np.isnan(xv), nan_ok, (xv >= lo) & (xv < hi)).astype(np.float64)
+        one = np.where(np.isnan(xv), nan_ok, (xv >= lo) & ~(xv >= hi)).astype(np.float64)
         z = [zero[:, e] for e in range(k)]
         o = [one[:, :, e] for e in range(k)]
         for a in range(k):

@@ -173,12 +173,12 @@ def extract_paths(b: Booster) -> tuple[np.ndarray, np.ndarray, np.ndarray, int]:
                 order: list[int] = []
                 for (parent, f, went_left, child) in path:
                     if f not in merged:
-                        merged[f] = [-np.inf, np.inf, True, 1.0]
+                        merged[f] = [-np.inf, np.nan, True, 1.0]  # hi = NaN: no upper bound (x = +inf follows)
                         order.append(f)
                     m = merged[f]
                     thr = float(t.split_conditions[parent])
                     if went_left:
-                        m[1] = min(m[1], thr)
+                        m[1] = thr if m[1] != m[1] else min(m[1], thr)
                     else:
                         m[0] = max(m[0], thr)
                     m[2] = m[2] and (bool(t.default_left[parent]) == went_left)
@@ -266,14 +266,28 @@ def _as_f32(X, device: torch.device) -> torch.Tensor:
     return torch.as_tensor(np.ascontiguousarray(np.asarray(X, dtype=np.float32)), device=device)
 
 
+def _check_kernel_rows(b: Booster, X: torch.Tensor) -> None:
+    """What the kernels assume of ``X`` and never look at themselves: float32 rows ``stride(0)`` apart with
+    unit column stride, at least as wide as the model (a tree reads ``x[feature]``). Raised before any
+    launch; :func:`_as_f32` brings any input into this form."""
+    if X.dim() != 2:
+        raise ValueError(f"X must be [rows, features], got shape {tuple(X.shape)}")
+    if X.dtype != torch.float32:
+        raise ValueError(f"X must be float32, got {X.dtype}")
+    if X.shape[1] > 1 and X.stride(1) != 1:
+        raise ValueError(f"X must have unit column stride, got stride {X.stride(1)}")
+    if X.shape[1] < b.num_feature:
+        raise ValueError(f"X has {X.shape[1]} features, model needs {b.num_feature}")
+
+
 def predict_gpu(b: Booster, X: torch.Tensor, n_trees: int | None = None, out_margin: torch.Tensor | None = None,
                 out_prob: torch.Tensor | None = None) -> None:
     """Launch the predictor on the current stream (graph-capturable: no host sync; small batches use a
-    scratch buffer from the caching allocator, which a graph capture takes from its private pool)."""
+    scratch buffer from the caching allocator, which a graph capture takes from its private pool).
+    ``X``: float32 with unit column stride (rows may be strided), else ``ValueError``."""
+    _check_kernel_rows(b, X)
     gf = gpu_forest(b, X.device, n_trees)
     N, F = X.shape
-    if F < b.num_feature:
-        raise ValueError(f"X has {F} features, model needs {b.num_feature}")
     lib = _native.lib()
     om = out_margin.data_ptr() if out_margin is not None else None
     op = out_prob.data_ptr() if out_prob is not None else None
@@ -296,9 +310,10 @@ _FORCE_DIRECT_SHAP = False  # tests compare the row-parallel table kernel agains
 
 def treeshap_gpu(b: Booster, X: torch.Tensor, phi: torch.Tensor) -> None:
     """Write TreeSHAP values into ``phi`` [N, F] float64 on the current stream (deterministic: no
-    floating-point atomics; partial sums are combined in a fixed order)."""
-    gf = gpu_forest(b, X.device, None, with_shap=True)
+    floating-point atomics; partial sums are combined in a fixed order). ``X`` as for :func:`predict_gpu`."""
+    _check_kernel_rows(b, X)
     N, F = X.shape
+    gf = gpu_forest(b, X.device, None, with_shap=True)
     lib = _native.lib()
     for s in range(0, N, 65535):
         e = min(N, s + 65535)
@@ -448,10 +463,13 @@ def shap_values(b: Booster, X, device=None):
     d = _device_of(X, device)
     if d.type == "cuda":
         Xt = _as_f32(X, d)
+        _check_kernel_rows(b, Xt)  # (a narrower X than the model: ValueError before anything is launched)
         phi = torch.zeros((Xt.shape[0], Xt.shape[1]), dtype=torch.float64, device=d)
         treeshap_gpu(b, Xt, phi)
         return phi if isinstance(X, torch.Tensor) else phi.cpu().numpy()
     Xn = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
+    if Xn.ndim != 2 or Xn.shape[1] < b.num_feature:
+        raise ValueError(f"X has shape {Xn.shape}, model needs [rows, >= {b.num_feature}]")
     return treeshap_host(b, Xn)
 
 
