@@ -135,3 +135,80 @@ def top_interactions(values, feature_names, k: int = 10) -> list[dict]:
     order = np.argsort(-strength, kind="stable")[:k]
     return [{"feature_a": feature_names[iu[q]], "feature_b": feature_names[ju[q]], "strength": float(strength[q])}
             for q in order]
+
+
+# --------------------------------------------------------------------------- partial dependence
+def partial_dependence(model, X, features, **kw) -> dict:
+    """Partial dependence / ICE curves (:meth:`Booster.partial_dependence`) of a ``GBDTClassifier``, a
+    ``Booster`` or a :class:`TreeExplainer`. A classifier scores the trees ``predict_proba`` scores (the first
+    ``best_iteration + 1`` of an early-stopped fit, or ``iteration_range=(0, n)``), on its device, and a
+    DataFrame's columns are reordered by feature name."""
+    if isinstance(model, TreeExplainer):
+        kw.setdefault("device", model.device)
+        return model.booster.partial_dependence(X, features, **kw)
+    if isinstance(model, Booster):
+        return model.partial_dependence(X, features, **kw)
+    if hasattr(model, "get_booster") and hasattr(model, "_n_trees"):
+        if "n_trees" in kw and "iteration_range" in kw:
+            raise ValueError("pass n_trees or iteration_range, not both")
+        if "n_trees" not in kw:
+            kw["n_trees"] = model._n_trees(kw.pop("iteration_range", None))
+        kw.setdefault("device", model.device)
+        return model.get_booster().partial_dependence(model._matrix(X), features, **kw)
+    raise TypeError("expected a GBDTClassifier, a Booster or a TreeExplainer")
+
+
+def pd_plot(result: dict, ice: bool = True, max_ice: int = 200, centered: bool = False):
+    """Draw a :func:`partial_dependence` result. One feature: the average as a line over at most ``max_ice``
+    evenly thinned ICE lines (``ice``, when the result has them); a NaN grid point ("feature missing") is
+    drawn apart, to the right of the numeric axis. ``centered``: every curve minus its value at the first
+    grid point. Two features: a filled contour of the average over the numeric grid."""
+    plt = _plt()
+    axes = [np.asarray(g, np.float64) for g in result["grid_values"]]
+    names = list(result["feature_names"])
+    avg = None if result.get("average") is None else np.asarray(result["average"], np.float64)
+    ind = None if result.get("individual") is None else np.asarray(result["individual"], np.float64)
+    if len(axes) == 2:
+        if avg is None:
+            raise ValueError("a two-feature plot needs the average (kind='average' or 'both')")
+        k0, k1 = ~np.isnan(axes[0]), ~np.isnan(axes[1])
+        z = avg[np.ix_(k0, k1)]
+        fig, ax = plt.subplots(figsize=(7, 5.5))
+        if z.shape[0] >= 2 and z.shape[1] >= 2:
+            cs = ax.contourf(axes[0][k0], axes[1][k1], z.T, levels=12, cmap="viridis")
+        else:
+            cs = ax.imshow(z.T, origin="lower", aspect="auto", cmap="viridis")
+        fig.colorbar(cs, ax=ax, label="partial dependence")
+        ax.set_xlabel(names[0])
+        ax.set_ylabel(names[1])
+        fig.tight_layout()
+        return fig
+    g = axes[0]
+    num = ~np.isnan(g)
+    fig, ax = plt.subplots(figsize=(8, 5))
+    # the missing point sits one step to the right of the numeric axis
+    gn = g[num]
+    span = float(gn.max() - gn.min()) if gn.size else 0.0
+    x_missing = (float(gn.max()) + (0.08 * span if span > 0 else 1.0)) if gn.size else 0.0
+
+    def draw(curve, **style):
+        c = curve - curve[0] if centered else curve
+        ax.plot(gn, c[num], **style)
+        if (~num).any():
+            ax.plot(np.full(int((~num).sum()), x_missing), c[~num], linestyle="none", marker="o",
+                    color=style.get("color"), alpha=style.get("alpha", 1.0), markersize=style.get("lw", 1.0) + 2)
+
+    if ice and ind is not None and len(ind):
+        pick = np.unique(np.linspace(0, len(ind) - 1, min(max_ice, len(ind))).astype(np.int64))
+        for r in pick:
+            draw(ind[r], color="#9ecae1", lw=0.6, alpha=0.5)
+    if avg is not None:
+        draw(avg, color="#08519c", lw=2.2)
+    if (~num).any():
+        ax.axvline(x_missing - (0.04 * span if span > 0 else 0.5), color="grey", lw=0.8, ls=":")
+        ticks = [t for t in ax.get_xticks() if gn.size and gn.min() <= t <= gn.max()]
+        ax.set_xticks(ticks + [x_missing], [f"{t:g}" for t in ticks] + ["missing"])
+    ax.set_xlabel(names[0])
+    ax.set_ylabel("partial dependence" + (" (centered)" if centered else ""))
+    fig.tight_layout()
+    return fig

@@ -257,6 +257,108 @@ class Booster:
 
         return predict_ops.shap_interaction_values(self, X, device=device)
 
+    def _feature_index(self, f) -> int:
+        """A feature given by index or by name (``feature_names``) as an index; ``ValueError`` otherwise."""
+        if isinstance(f, str):
+            names = self.feature_names or [f"f{i}" for i in range(self.num_feature)]
+            if f not in names:
+                raise ValueError(f"unknown feature name {f!r}")
+            return names.index(f)
+        if isinstance(f, (bool, float)) or not isinstance(f, (int, np.integer)):
+            raise ValueError(f"a feature is an index or a name, got {f!r}")
+        if not 0 <= int(f) < self.num_feature:
+            raise ValueError(f"feature index {int(f)} outside [0, {self.num_feature})")
+        return int(f)
+
+    def partial_dependence(self, X, features, *, grid=None, grid_resolution: int = 100,
+                           percentiles: tuple[float, float] = (0.05, 0.95), include_missing: bool = False,
+                           kind: str = "average", response: str = "probability", sample_weight=None,
+                           n_trees: int | None = None, device: str | None = None) -> dict[str, Any]:
+        """Partial dependence (PD) and individual conditional expectation (ICE) curves of one feature or a
+        pair (scikit-learn's ``partial_dependence(method="brute")``): every row of ``X`` is scored with the
+        feature(s) set to each grid value, everything else as in ``X`` (which is not modified).
+
+        ``features``: an index or a name, or a pair. ``grid``: explicit grid values (one array, or a pair of
+        arrays for two features; NaN = "the feature is missing"); by default each axis is built from the
+        column's non-NaN values: its unique values if there are fewer than ``grid_resolution``, else
+        ``grid_resolution`` points between the two ``percentiles``. ``include_missing`` appends a NaN point to
+        every axis. ``kind``: "average", "individual" or "both". ``response``: "probability" (the mean of the
+        per-row probabilities, not the sigmoid of the mean margin) or "margin" (log-odds). ``sample_weight``
+        weights the average. ``n_trees``: score that prefix of the forest.
+
+        Returns ``{"grid_values": [float32 axis, ...], "feature_names": [...], "average": float64 [G1] or
+        [G1, G2], "individual": float32 [N, G1] or [N, G1, G2]}`` (the last two as ``kind`` asks). On a GPU
+        one pass of ``csrc/pdp.hip`` per 16 grid points; ICE margins have the bits of ``predict_margin`` on
+        the substituted rows and the averages are reduced in a fixed order (same input, same bits)."""
+        from ..ops import predict_ops
+
+        if kind not in ("average", "individual", "both"):
+            raise ValueError(f"kind must be 'average', 'individual' or 'both', got {kind!r}")
+        if response not in ("probability", "margin"):
+            raise ValueError(f"response must be 'probability' or 'margin', got {response!r}")
+        if isinstance(features, (str, int, np.integer)):
+            features = [features]
+        features = list(features)
+        if len(features) not in (1, 2):
+            raise ValueError(f"partial dependence takes one or two features, got {len(features)}")
+        feats = [self._feature_index(f) for f in features]
+        if len(feats) == 2 and feats[0] == feats[1]:
+            raise ValueError(f"the two features must differ, got {features}")
+        names = self.feature_names or [f"f{i}" for i in range(self.num_feature)]
+        if hasattr(X, "columns") and self.feature_names:
+            X = X[self.feature_names]
+        if hasattr(X, "to_numpy"):
+            X = X.to_numpy(dtype=np.float32, na_value=np.nan)
+        if not hasattr(X, "shape") or len(X.shape) != 2:
+            X = np.asarray(X, dtype=np.float32)
+            if X.ndim != 2:
+                raise ValueError(f"X must be [rows, features], got shape {X.shape}")
+        N = int(X.shape[0])
+        if N == 0 or X.shape[1] < self.num_feature:
+            raise ValueError(f"X has shape {tuple(X.shape)}, model needs [rows >= 1, >= {self.num_feature}]")
+        w = None
+        if sample_weight is not None:
+            w = np.asarray(sample_weight.detach().cpu().numpy() if hasattr(sample_weight, "detach")
+                           else sample_weight, dtype=np.float32).reshape(-1)
+            if w.shape[0] != N:
+                raise ValueError(f"X has {N} rows, sample_weight has {w.shape[0]}")
+            if not bool((w >= 0).all()) or not float(np.sum(w, dtype=np.float64)) > 0:  # (NaN fails too)
+                raise ValueError("sample_weight must be non-negative with a positive sum")
+        if grid is None:
+            lo, hi = (float(q) for q in percentiles)
+            if not 0.0 <= lo < hi <= 1.0:
+                raise ValueError(f"percentiles must satisfy 0 <= low < high <= 1, got {percentiles}")
+            if int(grid_resolution) < 2:
+                raise ValueError(f"grid_resolution must be at least 2, got {grid_resolution}")
+            axes = []
+            for f in feats:
+                col = X[:, f]
+                col = col.detach().cpu().numpy() if hasattr(col, "detach") else np.asarray(col)
+                axes.append(pd_grid_axis(col, int(grid_resolution), (lo, hi)))
+        else:
+            given = [grid] if len(feats) == 1 else list(grid)
+            if len(given) != len(feats):
+                raise ValueError(f"{len(feats)} features need {len(feats)} grid axes, got {len(given)}")
+            axes = [np.asarray(g.detach().cpu().numpy() if hasattr(g, "detach") else g, dtype=np.float32)
+                    for g in given]
+        if include_missing:
+            axes = [np.concatenate([a.reshape(-1), np.array([np.nan], np.float32)]) for a in axes]
+        for a in axes:
+            if a.ndim != 1 or a.shape[0] == 0:
+                raise ValueError(f"a grid axis must be a non-empty vector, got shape {a.shape}")
+        want_ice = kind in ("individual", "both")
+        want_avg = kind in ("average", "both")
+        ice, avg_m, avg_p = predict_ops.partial_dependence(self, X, feats, axes, n_trees=n_trees, weights=w,
+                                                           want_ice=want_ice, want_avg=want_avg, device=device)
+        shape = tuple(len(a) for a in axes)
+        out: dict[str, Any] = {"grid_values": axes, "feature_names": [names[f] for f in feats]}
+        if want_avg:
+            out["average"] = np.asarray(avg_p if response == "probability" else avg_m, np.float64).reshape(shape)
+        if want_ice:
+            ind = np.ascontiguousarray(ice.T).reshape((N,) + shape)
+            out["individual"] = sigmoid32(ind) if response == "probability" else ind
+        return out
+
     def expected_value(self) -> float:
         """TreeExplainer ``expected_value``: base margin + cover-weighted mean leaf value per tree."""
         tot = 0.0
@@ -613,6 +715,55 @@ def eval_curve_host(b: Booster, X: np.ndarray, y, sample_weight=None, metrics: S
 def sigmoid32(m: np.ndarray) -> np.ndarray:
     m = np.asarray(m, dtype=np.float32)
     return (np.float32(1.0) / (np.float32(1.0) + np.exp(-m))).astype(np.float32)
+
+
+# ------------------------------------------------------------------------- partial dependence
+def partial_dependence_host(b: Booster, X: np.ndarray, feats: Sequence[int], grids: Sequence[np.ndarray],
+                            n_trees: int | None = None,
+                            weights: np.ndarray | None = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The definition of partial dependence / ICE (CPU path and oracle of ``csrc/pdp.hip``): for every grid
+    point ``k = i1 * G2 + i2`` a copy of ``X`` with column ``feats[0]`` set to ``grids[0][i1]`` (and
+    ``feats[1]`` to ``grids[1][i2]``; NaN = missing) is scored with :func:`predict_margin_host`.
+    Returns ``(ice, avg_margin, avg_prob)``: the margins [G, N] float32 and, per grid point, the weighted
+    means over the rows of the margin and of ``1 / (1 + exp(-m))`` (float64 from the float32 margin),
+    summed with ``math.fsum``. ``X`` is not modified."""
+    X = np.asarray(X, dtype=np.float32)
+    N = X.shape[0]
+    grids = [np.asarray(g, dtype=np.float32) for g in grids]
+    G2 = len(grids[1]) if len(feats) == 2 else 1
+    G = len(grids[0]) * G2
+    wd = np.ones(N, dtype=np.float64) if weights is None else np.asarray(weights, dtype=np.float32).astype(np.float64)
+    sw = math.fsum(wd)
+    ice = np.empty((G, N), dtype=np.float32)
+    avg_m = np.empty(G, dtype=np.float64)
+    avg_p = np.empty(G, dtype=np.float64)
+    Xs = X.copy()
+    for k in range(G):
+        i1, i2 = divmod(k, G2)
+        Xs[:, feats[0]] = grids[0][i1]
+        if len(feats) == 2:
+            Xs[:, feats[1]] = grids[1][i2]
+        ice[k] = predict_margin_host(b, Xs, n_trees)
+        m = ice[k].astype(np.float64)
+        with np.errstate(over="ignore"):
+            p = 1.0 / (1.0 + np.exp(-m))
+        avg_m[k] = math.fsum(wd * m) / sw
+        avg_p[k] = math.fsum(wd * p) / sw
+    return ice, avg_m, avg_p
+
+
+def pd_grid_axis(col: np.ndarray, grid_resolution: int, percentiles: tuple[float, float]) -> np.ndarray:
+    """One axis of a partial-dependence grid by scikit-learn's rule, from the non-NaN values of a column: its
+    unique values when there are fewer than ``grid_resolution`` of them, else ``grid_resolution`` points from
+    the lower to the upper percentile (linear interpolation), as float32."""
+    vals = col[~np.isnan(col)]
+    if vals.size == 0:
+        raise ValueError("the column has no non-missing value: pass an explicit grid")
+    uniq = np.unique(vals)
+    if uniq.shape[0] < grid_resolution:
+        return uniq.astype(np.float32)
+    lo, hi = (np.quantile(vals, q) for q in percentiles)
+    return np.linspace(lo, hi, grid_resolution).astype(np.float32)
 
 
 def treeshap_host(b: Booster, X: np.ndarray) -> np.ndarray:

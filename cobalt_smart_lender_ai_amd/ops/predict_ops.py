@@ -2,7 +2,7 @@
 :class:`Booster`.
 
 GPU path: gfx950 kernels in ``csrc/predict.hip`` (forest packed once per booster and device, cached),
-``csrc/shapint.hip`` and ``csrc/evalcurve.hip``.
+``csrc/shapint.hip``, ``csrc/evalcurve.hip`` and ``csrc/pdp.hip``.
 CPU path: the NumPy reference implementations in ``models/booster.py``.
 """
 from __future__ import annotations
@@ -15,8 +15,9 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..models.booster import (Booster, Tree, check_eval_inputs, eval_curve_host, predict_margin_host, sigmoid32,
-                              staged_margins_host, treeshap_host, treeshap_interactions_host)
+from ..models.booster import (Booster, Tree, check_eval_inputs, eval_curve_host, partial_dependence_host,
+                              predict_margin_host, sigmoid32, staged_margins_host, treeshap_host,
+                              treeshap_interactions_host)
 from ..config import knob
 
 # LDS tile capacity in nodes: a model's tile is max(this, its largest tree), at most MAX_TILE_NODES
@@ -73,6 +74,19 @@ _native.register("cobalt_eval_curve", ctypes.c_int,
                   ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                   ctypes.c_void_p, ctypes.c_void_p])
 _native.register("cobalt_eval_curve_workspace", ctypes.c_int64, [ctypes.c_int64, ctypes.c_int])
+
+# csrc/pdp.hip: (X, n, F, ldx, nodes, tree_ptr, tile_ptr, n_tiles, tile_cap, base_margin, f1, f2, g1, G1, g2, G2,
+# w, ice, workspace, sums, stream)
+_native.register("cobalt_pdp", ctypes.c_int,
+                 [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_int,
+                  ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p])
+_native.register("cobalt_pdp_workspace", ctypes.c_int64, [ctypes.c_int64, ctypes.c_int])
+_native.register("cobalt_pdp_grid_chunk", ctypes.c_int, [])
+_native.register("cobalt_pdp_chunk_rows", ctypes.c_int64, [])
+_native.register("cobalt_pdp_max_grid", ctypes.c_int, [])
+PDP_MAX_GRID = 1 << 16         # grid points per call (csrc/pdp.hip kPdpMaxGrid)
 
 PATH_ELEM = np.dtype([("lo", "<f4"), ("hi", "<f4"), ("feat", "<i4"), ("nan_ok", "<i4"), ("zero", "<f8")])
 
@@ -457,6 +471,93 @@ def staged_margins(b: Booster, X, device=None):
     if b.num_trees and Xt.shape[0]:
         _eval_curve_launch(b, Xt, None, None, None, None, stages)
     return stages if isinstance(X, torch.Tensor) else stages.cpu().numpy()
+
+
+# --------------------------------------------------------------------------- partial dependence
+def _check_pd_args(b: Booster, feats, grids) -> tuple[tuple[int, ...], list[np.ndarray]]:
+    """Features as a tuple of one or two distinct indices inside the model, grids as non-empty float32
+    vectors (one per feature; NaN = the feature is missing). ``ValueError`` otherwise."""
+    feats = tuple(int(f) for f in feats)
+    if len(feats) not in (1, 2):
+        raise ValueError(f"partial dependence takes one or two features, got {len(feats)}")
+    for f in feats:
+        if not 0 <= f < b.num_feature:
+            raise ValueError(f"feature index {f} outside [0, {b.num_feature})")
+    if len(feats) == 2 and feats[0] == feats[1]:
+        raise ValueError(f"the two features must differ, got {feats}")
+    if len(grids) != len(feats):
+        raise ValueError(f"{len(feats)} features need {len(feats)} grids, got {len(grids)}")
+    out = []
+    for g in grids:
+        g = g.detach().cpu().numpy() if isinstance(g, torch.Tensor) else np.asarray(g)
+        g = np.ascontiguousarray(g, dtype=np.float32)
+        if g.ndim != 1 or g.shape[0] == 0:
+            raise ValueError(f"a grid axis must be a non-empty vector, got shape {g.shape}")
+        out.append(g)
+    return feats, out
+
+
+def partial_dependence_gpu(b: Booster, X: torch.Tensor, feats, grids, *, n_trees: int | None = None,
+                           weights: torch.Tensor | None = None, want_ice: bool,
+                           want_avg: bool) -> tuple[torch.Tensor | None, torch.Tensor | None]:
+    """Launch ``csrc/pdp.hip`` on the current stream (no host sync). Grid point ``k = i1 * G2 + i2`` scores
+    every row with ``x[feats[0]] = grids[0][i1]`` (and ``x[feats[1]] = grids[1][i2]``); ``X`` is not written.
+    Returns ``(ice, sums)``: ``ice`` [G, N] float32 margins with the bits of ``predict_margin`` on the
+    substituted rows (``want_ice``), ``sums`` [2 G + 1] float64 = (sum w m, sum w p) per grid point, then
+    sum w (``want_avg``; deterministic: fixed reduction order, no floating-point atomics). ``X`` as for
+    :func:`predict_gpu`; ``weights``: float32 [N] on the device of ``X``. ``ValueError`` / ``RuntimeError``
+    (a model outside the kernel's LDS limits) before anything is launched."""
+    _check_kernel_rows(b, X)
+    feats, grids = _check_pd_args(b, feats, grids)
+    N, F = X.shape
+    G1 = len(grids[0])
+    G2 = len(grids[1]) if len(feats) == 2 else 1
+    G = G1 * G2
+    if G > PDP_MAX_GRID:
+        raise ValueError(f"{G} grid points exceed the limit of {PDP_MAX_GRID} per call")
+    if weights is not None and (weights.dtype != torch.float32 or weights.dim() != 1 or weights.shape[0] != N
+                                or weights.device != X.device or not weights.is_contiguous()):
+        raise ValueError(f"weights must be a contiguous float32 [{N}] tensor on {X.device}")
+    gf = gpu_forest(b, X.device, n_trees)
+    lib = _native.lib()
+    g1 = torch.from_numpy(grids[0]).to(X.device)
+    g2 = torch.from_numpy(grids[1]).to(X.device) if len(feats) == 2 else None
+    ice = torch.empty((G, N), dtype=torch.float32, device=X.device) if want_ice else None
+    sums = work = None
+    if want_avg:
+        sums = torch.zeros(2 * G + 1, dtype=torch.float64, device=X.device)
+        work = torch.empty(int(lib.cobalt_pdp_workspace(N, G)), dtype=torch.uint8, device=X.device)
+    rc = lib.cobalt_pdp(X.data_ptr(), N, F, X.stride(0), gf.nodes.data_ptr(), gf.tree_ptr.data_ptr(),
+                        gf.tile_ptr.data_ptr(), gf.n_tiles, gf.tile_cap, b.base_margin, feats[0],
+                        feats[1] if len(feats) == 2 else -1, g1.data_ptr(), G1, _native.ptr(g2), G2,
+                        _native.ptr(weights), _native.ptr(ice), _native.ptr(work), _native.ptr(sums),
+                        _native.stream_handle())
+    _native.check(rc, "cobalt_pdp")
+    return ice, sums
+
+
+def partial_dependence(b: Booster, X, feats, grids, *, n_trees: int | None = None, weights=None,
+                       want_ice: bool = True, want_avg: bool = True, device=None):
+    """``(ice, avg_margin, avg_prob)`` as NumPy: ICE margins [G, N] float32 (None without ``want_ice``) and
+    the weighted means over the rows of the margin and of the probability, float64 [G] (None without
+    ``want_avg``), at the grid points ``k = i1 * G2 + i2``. A CUDA device runs ``csrc/pdp.hip``, the CPU runs
+    :func:`~..models.booster.partial_dependence_host` (the definition)."""
+    d = _device_of(X, device)
+    w32 = None if weights is None else _host_vec(weights)
+    if d.type != "cuda":
+        Xn = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
+        feats, grids = _check_pd_args(b, feats, grids)
+        ice, am, ap = partial_dependence_host(b, Xn, feats, grids, n_trees, w32)
+        return (ice if want_ice else None), (am if want_avg else None), (ap if want_avg else None)
+    Xt = _as_f32(X, d)
+    wt = None if w32 is None else torch.as_tensor(w32, device=d)
+    ice, sums = partial_dependence_gpu(b, Xt, feats, grids, n_trees=n_trees, weights=wt, want_ice=want_ice,
+                                       want_avg=want_avg)
+    am = ap = None
+    if sums is not None:
+        s = sums.cpu().numpy()
+        am, ap = s[0:-1:2] / s[-1], s[1:-1:2] / s[-1]
+    return (None if ice is None else ice.cpu().numpy()), am, ap
 
 
 def shap_values(b: Booster, X, device=None):
