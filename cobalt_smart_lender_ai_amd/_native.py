@@ -43,6 +43,8 @@ _SIGS: dict[str, tuple] = {
     "cobalt_heap_to_trees": (ctypes.c_int64, [c_void_p, c_int, c_int] + [c_void_p] * 10),
     "cobalt_gbdt_set_data": (c_int, [c_void_p] * 9),
     "cobalt_gbdt_grow": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "cobalt_gbdt_reorder": (c_int, [c_void_p, c_int, c_void_p]),
+    "cobalt_gbdt_unpermute": (c_int, [c_void_p, c_void_p]),
     "cobalt_gbdt_fetch_trees": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "cobalt_gbdt_max_nodes": (c_int, [c_void_p]),
     "cobalt_gbdt_set_start": (c_int, [c_void_p, c_int]),

@@ -231,6 +231,10 @@ struct GbdtDev {
   // wide gradients (grad_bits 25): |g_q| < 2^25, h_q <= 2^25, and the LDS histograms hold a cell as two
   // int64 words (g, h) -- ds_add_u64 each -- instead of one packed u64; slabs likewise (see kWide)
   int32_t wide;
+  // row reorder (cobalt_gbdt_reorder): the rows sit grouped by the leaf they reached in an earlier tree;
+  // orig[p] = the original local row at position p, which keys the per-row hashes (subsample, dither).
+  // nullptr: the rows are in their original order
+  const int32_t* orig;
 };
 
 
@@ -560,12 +564,13 @@ __global__ __launch_bounds__(256) void k_grad(GbdtDev d, int tree, int apply_tre
     const double w = d.ylab ? (double)(yf != 0.0f ? d.spw : 1.0f) : (double)d.weight[i];
     double g = (p - y) * w;
     double h = fmax(p * (1.0 - p), 1e-16) * w;
+    const int64_t gi = d.row_offset + (d.orig ? (int64_t)d.orig[i] : i);  // the hashes' key: the global row
     if (d.subsample < 1.0) {
-      const uint64_t hsh = splitmix64(tree_key ^ (uint64_t)(d.row_offset + i));
+      const uint64_t hsh = splitmix64(tree_key ^ (uint64_t)gi);
       if (!(uniform01(hsh) < d.subsample)) { g = 0.0; h = 0.0; }
     }
     int64_t gq, hq;
-    quantize_gh(g, h, d.gscale, d.hscale, dkey, d.row_offset + i, gq, hq, d.wide != 0);
+    quantize_gh(g, h, d.gscale, d.hscale, dkey, gi, gq, hq, d.wide != 0);
     if (rec32) {
       rb.z = (uint32_t)hq | (d.lab31 ? lbit : 0u);
       rb.w = (uint32_t)(int32_t)gq;
@@ -1116,6 +1121,7 @@ __device__ __forceinline__ void grad_hist_body(const GbdtDev& d, int tree, int a
   for (int64_t i0 = begin + threadIdx.x; i0 < end; i0 += U * B) {
     uint4 ra[U], rb[U];
     float mf[U], yl[U], wt[U];
+    int32_t og[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t i = i0 + (int64_t)u * B;
@@ -1124,6 +1130,7 @@ __device__ __forceinline__ void grad_hist_body(const GbdtDev& d, int tree, int a
       ra[u] = rec[0];
       rb[u] = rec[1];
       mf[u] = d.mrec ? 0.0f : d.margin[ii];
+      og[u] = d.orig ? d.orig[ii] : (int32_t)i;  // (reordered rows: loaded with the record)
       yl[u] = 0.0f;
       wt[u] = 0.0f;
       if (!d.ylab) {
@@ -1156,12 +1163,13 @@ __device__ __forceinline__ void grad_hist_body(const GbdtDev& d, int tree, int a
       const double w = (double)wt[u];
       double g = (p - y) * w;
       double h = fmax(p * (1.0 - p), 1e-16) * w;
+      const int64_t gi = d.row_offset + (int64_t)og[u];  // the hashes' key: the global row
       if (d.subsample < 1.0) {
-        const uint64_t hsh = splitmix64(tree_key ^ (uint64_t)(d.row_offset + i));
+        const uint64_t hsh = splitmix64(tree_key ^ (uint64_t)gi);
         if (!(uniform01(hsh) < d.subsample)) { g = 0.0; h = 0.0; }
       }
       int64_t gq, hq;
-      quantize_gh(g, h, d.gscale, d.hscale, dkey, d.row_offset + i, gq, hq, kWide);
+      quantize_gh(g, h, d.gscale, d.hscale, dkey, gi, gq, hq, kWide);
       tg += gq;
       th += hq;
       rb[u].y = d.mrec ? (uint32_t)__float_as_int(mf[u]) : rb[u].y;
@@ -3137,6 +3145,21 @@ struct GbdtCtx {
   float* ox_margin = nullptr;
   const float* ox_label = nullptr;
   const float* ox_weight = nullptr;
+  // row reorder (cobalt_gbdt_reorder): two sets of per-row buffers of the context's own (allocated at the
+  // first reorder, kept with the context), written alternately; ro_cur = the set the trainer reads (-1: the
+  // caller's arrays, rows in their original order). The caller's arrays are never permuted.
+  uint8_t* ro_rec[2] = {nullptr, nullptr};
+  uint8_t* ro_T[2] = {nullptr, nullptr};
+  float* ro_margin[2] = {nullptr, nullptr};
+  float* ro_label[2] = {nullptr, nullptr};
+  float* ro_weight[2] = {nullptr, nullptr};
+  int32_t* ro_orig[2] = {nullptr, nullptr};
+  int32_t* ro_src = nullptr;   // [n] position -> the position it is filled from
+  uint16_t* ro_key = nullptr;  // [n] sort keys
+  int32_t* ro_cnt = nullptr;   // [keys][chunks] bucket counts -> offsets
+  int ro_cur = -1;
+  int ro_done = 0;             // reorders of the current fit
+  GbdtDev ro_user{};           // the caller's arrays (bins, binsT, margin, label, weight)
 };
 
 // Next launch's stamp slot (0 when stamping is off or the tree is not sampled: d.stamps == nullptr).
@@ -3480,6 +3503,9 @@ COBALT_API int cobalt_gbdt_set_data(void* h, uint8_t* bins, const uint8_t* binsT
   c->label_pending = false;
   c->d.margin = margin;
   c->d.fmask = fmask;
+  c->d.orig = nullptr;  // (rows in the caller's order: cobalt_gbdt_reorder)
+  c->ro_cur = -1;
+  c->ro_done = 0;
   // Histogram LDS layout from the per-feature bin counts (one small synchronous copy per fit).
   const int F = c->d.F, ft = c->d.feat_tile, ntiles = ceil_div(F, ft);
   std::vector<int32_t> nb(F);
@@ -3596,7 +3622,7 @@ static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool s
   // ms per fit; at 1.25M the copy-in / copy-out launches and the lost write-through of (g, h) cost more
   // (78.2 / 78.9 vs 77.2 / 77.0; profiles/round6/ab_margin_in_record.txt). COBALT_MARGIN_IN_RECORD: 0 off,
   // 2 at any size
-  static const int env_mrec = knob_int(Knob::MarginInRecord, 1);
+  const int env_mrec = knob_int(Knob::MarginInRecord, 1);  // (per call: a test switches it between fits)
   d.mrec = (env_mrec != 0 && d.lab31 && fuse_root && d.n > 0 && (env_mrec == 2 || d.n >= 4000000)) ? 1 : 0;
   {
     const dim3 g1(std::max(1, std::min(ceil_div(d.n, 256), 4096)));
@@ -3903,6 +3929,247 @@ static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool s
 
 COBALT_API int cobalt_gbdt_grow(void* h, int t0, int n_trees, hipStream_t stream) {
   return grow_impl(static_cast<GbdtCtx*>(h), t0, n_trees, stream, false);
+}
+
+// ------------------------------------------------------------------------------------------
+// Row reorder. k_hist and k_part_pos gather through a node's row ids, and a node's rows are scattered
+// over all n rows: at the deep levels every gathered 32-byte record costs its own 64-byte transfer and
+// every gathered bin byte its own sector. The model does not depend on the row order (exact integer
+// histogram sums; the per-row hashes are keyed by the global row, GbdtDev::orig), and boosted trees at a
+// small eta are alike from round to round -- so between two grow calls the rows are regrouped by the leaf
+// they reached in a grown tree, and the next trees' nodes are long runs of consecutive positions
+// (scripts/row_locality.py counts the units touched). One reorder is
+//   k_reorder_key      walk tree `tree` over every record: key = the leaf's left-most bottom-level position
+//                      (depth-first order: every subtree's rows are contiguous), 2 bytes per row;
+//   k_reorder_count    per 2048-row wave chunk, the rows per key (LDS counters, no global atomics);
+//   k_reorder_scan     exclusive scan of the [key][chunk] counts: every (key, chunk)'s first position;
+//   k_reorder_scatter  src[new position] = old position, stable (ranks within a wave by ballots), so
+//                      repeated reorders are hierarchical: the latest tree is the primary key;
+//   k_reorder_apply    position p takes the whole record of src[p] (two 16-byte loads and stores), its
+//                      margin, label, weight and original row, and the feature-major bytes of p are
+//                      written from the record's own bins (binsT is not gathered at all)
+// into the context's second set of buffers, which the trainer then reads. No host synchronisation.
+// ------------------------------------------------------------------------------------------
+constexpr int kRoChunk = 2048;  // rows per wave of the counting sort
+constexpr int kRoWaves = 4;     // waves per block
+
+__global__ __launch_bounds__(256) void k_reorder_key(GbdtDev d, int tree, uint16_t* __restrict__ key) {
+  extern __shared__ uint32_t s_tree[];
+  uint32_t* s_meta = s_tree;
+  float* s_leaf = reinterpret_cast<float*>(s_tree + d.max_nodes);
+  stage_tree(d, d.trees + (int64_t)tree * d.max_nodes, s_meta, s_leaf);
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint4* rec = reinterpret_cast<const uint4*>(d.bins + i * 32);
+    const uint4 ra = rec[0], rb = rec[1];
+    int n = 0, level = 0;
+    uint32_t m = s_meta[0];
+    while ((m & kMetaSplit) && level < d.max_depth) {
+      const int f = m & 0xFFFF, q = f >> 2;
+      const uint32_t word = q == 0 ? ra.x : q == 1 ? ra.y : q == 2 ? ra.z : q == 3 ? ra.w : q == 4 ? rb.x : rb.y;
+      const uint32_t b = (word >> (8 * (f & 3))) & 0xffu;
+      n = 2 * n + (meta_left(m, b) ? 1 : 2);
+      ++level;
+      m = s_meta[n];
+    }
+    key[i] = (uint16_t)(((n + 1) << (d.max_depth - level)) - (1 << d.max_depth));
+  }
+}
+
+// Wave w of block b sorts chunk c = b * kRoWaves + w: rows [c * kRoChunk, (c + 1) * kRoChunk). Every wave
+// runs the same kRoChunk / 64 steps (rows past n are masked), so the block barriers are uniform.
+__global__ __launch_bounds__(kRoWaves * 64) void k_reorder_count(const uint16_t* __restrict__ key, int64_t n, int nk,
+                                                                 int nchunks, int32_t* __restrict__ cnt) {
+  extern __shared__ int32_t s_ro[];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int chunk = blockIdx.x * kRoWaves + w;
+  int32_t* my = s_ro + w * nk;
+  for (int k = lane; k < nk; k += 64) my[k] = 0;
+  __syncthreads();
+  for (int it = 0; it < kRoChunk / 64; ++it) {
+    const int64_t i = (int64_t)chunk * kRoChunk + it * 64 + lane;
+    if (chunk < nchunks && i < n) atomicAdd(&my[min((int)key[i], nk - 1)], 1);
+  }
+  __syncthreads();
+  if (chunk < nchunks)
+    for (int k = lane; k < nk; k += 64) cnt[(int64_t)k * nchunks + chunk] = my[k];
+}
+
+// In-place exclusive scan of `total` counts by one 1024-thread block, 4096 per step.
+__global__ __launch_bounds__(1024) void k_reorder_scan(int32_t* __restrict__ a, int total) {
+  __shared__ int32_t s_w[16];
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  int32_t carry = 0;
+  for (int base = 0; base < total; base += 4096) {
+    const int idx = base + tid * 4;
+    int32_t v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = idx + j < total ? a[idx + j] : 0;
+    const int32_t s = v[0] + v[1] + v[2] + v[3];
+    int32_t inc = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int32_t up = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += up;
+    }
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    int32_t before = 0, all = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int32_t t = s_w[k];
+      before += k < w ? t : 0;
+      all += t;
+    }
+    int32_t run = carry + before + inc - s;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (idx + j < total) a[idx + j] = run;
+      run += v[j];
+    }
+    carry += all;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kRoWaves * 64) void k_reorder_scatter(const uint16_t* __restrict__ key, int64_t n, int nk,
+                                                                   int nchunks, const int32_t* __restrict__ off,
+                                                                   int32_t* __restrict__ src) {
+  extern __shared__ int32_t s_ro[];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int chunk = blockIdx.x * kRoWaves + w;
+  int32_t* my = s_ro + w * nk;
+  if (chunk < nchunks)
+    for (int k = lane; k < nk; k += 64) my[k] = off[(int64_t)k * nchunks + chunk];
+  __syncthreads();
+  for (int it = 0; it < kRoChunk / 64; ++it) {
+    const int64_t i = (int64_t)chunk * kRoChunk + it * 64 + lane;
+    const bool valid = chunk < nchunks && i < n;
+    const int k = valid ? min((int)key[i], nk - 1) : -1;
+    // rank among the wave's rows of the same key (lane order = row order: the sort is stable)
+    int rank = 0, same = 0;
+    bool leader = false;
+    uint64_t rem = __ballot(valid);
+    while (rem) {
+      const int l = __ffsll((unsigned long long)rem) - 1;
+      const int k0 = __shfl(k, l, 64);
+      const uint64_t mk = __ballot(valid && k == k0);
+      if (valid && k == k0) {
+        rank = __popcll(mk & ((1ull << lane) - 1ull));
+        same = __popcll(mk);
+        leader = lane == l;
+      }
+      rem &= ~mk;
+    }
+    const int32_t first = valid ? my[k] : 0;
+    __syncthreads();
+    if (valid && (int64_t)first + rank < n) src[first + rank] = (int32_t)i;
+    if (leader) my[k] = first + same;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void k_reorder_apply(GbdtDev d, const int32_t* __restrict__ src, uint8_t* __restrict__ rec_o,
+                                                       uint8_t* __restrict__ T_o, float* __restrict__ margin_o,
+                                                       float* __restrict__ label_o, float* __restrict__ weight_o,
+                                                       int32_t* __restrict__ orig_o) {
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < d.n; p += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t s = min((int64_t)(uint32_t)src[p], d.n - 1);
+    const uint4* rec = reinterpret_cast<const uint4*>(d.bins + s * 32);
+    const uint4 ra = rec[0], rb = rec[1];
+    uint4* out = reinterpret_cast<uint4*>(rec_o + p * 32);
+    out[0] = ra;
+    out[1] = rb;
+    margin_o[p] = d.margin[s];
+    if (!d.ylab) {
+      label_o[p] = d.label[s];
+      weight_o[p] = d.weight[s];
+    }
+    orig_o[p] = d.orig ? d.orig[s] : (int32_t)s;
+    const uint32_t wd[6] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y};
+#pragma unroll
+    for (int f = 0; f < 24; ++f)
+      if (f < d.F) T_o[(int64_t)f * d.ldt + p] = (uint8_t)(wd[f >> 2] >> (8 * (f & 3)));
+  }
+}
+
+__global__ __launch_bounds__(256) void k_reorder_margin_out(const float* __restrict__ margin, const int32_t* __restrict__ orig,
+                                                            float* __restrict__ out, int64_t n) {
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t o = orig[p];
+    if (o >= 0 && o < n) out[o] = margin[p];
+  }
+}
+
+// Regroup the rows by their leaf in the grown tree `tree`, between two grow calls. Returns 1 (nothing
+// done) where reordering does not apply: generic or wide records, data parallelism, a sampled row set.
+COBALT_API int cobalt_gbdt_reorder(void* h, int tree, hipStream_t stream) {
+  GbdtCtx* c = static_cast<GbdtCtx*>(h);
+  GbdtDev& d = c->d;
+  if (tree < 0 || tree >= c->grown || c->applied != c->grown) return -11;
+  if (hist_ft4(d) == 0 || d.wide || c->cfg.comm || d.n != d.ldt || d.n < 1 || d.mrec) return 1;
+  const int nk = 1 << d.max_depth;
+  const int nchunks = ceil_div(d.n, kRoChunk);
+  const int64_t total = (int64_t)nk * nchunks;
+  if (total > (1 << 24)) return 1;
+  const int64_t N = c->cfg.n_rows;
+  if (!c->ro_src) {  // the context's own per-row buffers, once (kept over cobalt_gbdt_reuse)
+    int rc = 0;
+    for (int k = 0; k < 2; ++k) {
+      if ((rc = dev_alloc(c, (void**)&c->ro_rec[k], (size_t)N * 32))) return rc;
+      if ((rc = dev_alloc(c, (void**)&c->ro_T[k], (size_t)N * d.F))) return rc;
+      if ((rc = dev_alloc(c, (void**)&c->ro_margin[k], (size_t)N * sizeof(float)))) return rc;
+      if ((rc = dev_alloc(c, (void**)&c->ro_label[k], (size_t)N * sizeof(float)))) return rc;
+      if ((rc = dev_alloc(c, (void**)&c->ro_weight[k], (size_t)N * sizeof(float)))) return rc;
+      if ((rc = dev_alloc(c, (void**)&c->ro_orig[k], (size_t)N * sizeof(int32_t)))) return rc;
+    }
+    if ((rc = dev_alloc(c, (void**)&c->ro_key, (size_t)N * sizeof(uint16_t)))) return rc;
+    if ((rc = dev_alloc(c, (void**)&c->ro_cnt, (size_t)nk * ceil_div(N, kRoChunk) * sizeof(int32_t)))) return rc;
+    if ((rc = dev_alloc(c, (void**)&c->ro_src, (size_t)N * sizeof(int32_t)))) return rc;
+  }
+  if (c->ro_cur < 0) c->ro_user = d;
+  const int nxt = c->ro_cur < 0 ? 0 : c->ro_cur ^ 1;
+  const dim3 g1(std::max(1, std::min(ceil_div(d.n, 256), 4096)));
+  const dim3 gs(ceil_div(nchunks, kRoWaves));
+  const size_t sort_lds = (size_t)kRoWaves * nk * sizeof(int32_t);
+  hipLaunchKernelGGL(k_reorder_key, g1, dim3(256), (size_t)c->max_nodes * 8, stream, d, tree, c->ro_key);
+  hipLaunchKernelGGL(k_reorder_count, gs, dim3(kRoWaves * 64), sort_lds, stream, c->ro_key, d.n, nk, nchunks, c->ro_cnt);
+  hipLaunchKernelGGL(k_reorder_scan, dim3(1), dim3(1024), 0, stream, c->ro_cnt, (int)total);
+  hipLaunchKernelGGL(k_reorder_scatter, gs, dim3(kRoWaves * 64), sort_lds, stream, c->ro_key, d.n, nk, nchunks, c->ro_cnt,
+                     c->ro_src);
+  hipLaunchKernelGGL(k_reorder_apply, g1, dim3(256), 0, stream, d, c->ro_src, c->ro_rec[nxt], c->ro_T[nxt],
+                     c->ro_margin[nxt], c->ro_label[nxt], c->ro_weight[nxt], c->ro_orig[nxt]);
+  CK_LAUNCH();
+  d.bins = c->ro_rec[nxt];
+  d.binsT = c->ro_T[nxt];
+  d.margin = c->ro_margin[nxt];
+  if (!d.ylab) {
+    d.label = c->ro_label[nxt];
+    d.weight = c->ro_weight[nxt];
+  }
+  d.orig = c->ro_orig[nxt];
+  c->ro_cur = nxt;
+  ++c->ro_done;
+  return 0;
+}
+
+// End of a reordered fit: the margins back into the caller's array in the original row order, and the
+// caller's arrays bound again. Nothing to do (0) when the rows were never reordered.
+COBALT_API int cobalt_gbdt_unpermute(void* h, hipStream_t stream) {
+  GbdtCtx* c = static_cast<GbdtCtx*>(h);
+  GbdtDev& d = c->d;
+  if (c->ro_cur < 0) return 0;
+  hipLaunchKernelGGL(k_reorder_margin_out, dim3(std::max(1, std::min(ceil_div(d.n, 256), 4096))), dim3(256), 0, stream,
+                     d.margin, d.orig, c->ro_user.margin, d.n);
+  CK_LAUNCH();
+  d.bins = c->ro_user.bins;
+  d.binsT = c->ro_user.binsT;
+  d.margin = c->ro_user.margin;
+  d.label = c->ro_user.label;
+  d.weight = c->ro_user.weight;
+  d.orig = nullptr;
+  c->ro_cur = -1;
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -4336,6 +4603,9 @@ COBALT_API int cobalt_gbdt_reuse(void* h, const GbdtConfig* cfg) {
   c->fault_tree = -1;
   c->mono_on = false;  // (the next fit sets its own constraints, if any)
   c->inter_on = false;
+  d.orig = nullptr;  // (the reorder buffers stay; set_data binds the next fit's arrays)
+  c->ro_cur = -1;
+  c->ro_done = 0;
   if (c->err_pinned) memset(c->err_pinned, 0, 64);
   return 0;
 }

@@ -79,6 +79,10 @@ class GBDTParams:
     # "[[0, 1], [2, 3]]". Features may share a root-to-leaf path only when one group holds them all.
     # None / [] / "" / "[]": the unconstrained fit. See :func:`resolve_interaction`.
     interaction_constraints: Any = None
+    # trees after which the GPU trainer regroups the training rows by the leaf they reached (the model and
+    # the returned margins do not depend on it; see :func:`resolve_row_reorder`): a list of tree indices, an
+    # int period, the string forms "0,8,32" / "every:16" / "off". None: COBALT_ROW_REORDER
+    row_reorder: Any = None
 
     @classmethod
     def from_kwargs(cls, **kw) -> "GBDTParams":
@@ -526,6 +530,36 @@ def interaction_words(groups: list[list[int]], n_features: int) -> np.ndarray:
     return w
 
 
+# COBALT_ROW_REORDER=auto: the schedule by local row count (docs/PERF.md "Row reorder")
+# (same-box A/B against the parent, profiles/round7/ab_row_reorder.txt: 10M rows 222.8 -> 206.0 ms per fit,
+# 5M 142.6 -> 136.7, 2.5M 99.6 -> 95.6, 1.25M 73.4 -> 71.5; below 1M rows not measured: off)
+ROW_REORDER_AUTO: list[tuple[int, str]] = [(1_000_000, "0"), (8_000_000, "0,8,32,128")]  # (min rows, schedule)
+
+
+def resolve_row_reorder(spec, n_trees: int, n_rows: int) -> list[int]:
+    """Tree indices after which the rows are regrouped (sorted, < n_trees - 1: a reorder after the last
+    tree serves nothing). ``spec``: None (the COBALT_ROW_REORDER knob), a sequence of tree indices, an int
+    period (0: off) or "0,8,32" / "every:16" / "off" / "" / "auto"."""
+    if spec is None:
+        spec = knob("COBALT_ROW_REORDER", "auto")
+    if isinstance(spec, str):
+        s = spec.strip().lower()
+        if s == "auto":
+            s = "off"
+            for min_rows, sched in ROW_REORDER_AUTO:
+                if n_rows >= min_rows:
+                    s = sched
+        if s in ("", "off"):
+            return []
+        spec = int(s[6:]) if s.startswith("every:") else [int(t) for t in s.split(",") if t.strip()]
+    if isinstance(spec, (int, np.integer)):
+        spec = range(0, n_trees, int(spec)) if int(spec) > 0 else []
+    out = sorted({int(t) for t in spec})
+    if out and out[0] < 0:
+        raise ValueError("row_reorder: tree indices must be >= 0")
+    return [t for t in out if t < n_trees - 1]
+
+
 def check_grad_bits(grad_bits: int, n_features: int, device_type: str) -> None:
     """``grad_bits`` is 17 or 25; the GPU's wide (25-bit) cells need the 32-byte row records of <= 24
     features (csrc/gbdt.hip cobalt_gbdt_create refuses the rest with -6)."""
@@ -902,6 +936,28 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
             tr.set_monotone(mono)
         if inter is not None:
             tr.set_interaction(interaction_words(inter, F), len(inter))
+        # row reorder: one process, in core, 32-byte records, 17-bit gradients, a fresh model, no checkpoints
+        ro_sched = resolve_row_reorder(params.row_reorder, T, N)
+        ro_off = ("data parallel" if world > 1 else "init_booster" if init_booster is not None or T0
+                  else "checkpointing" if checkpoint is not None
+                  else "generic records" if bd.records.shape[1] != 32 or F > 24
+                  else "wide gradients" if grad_bits != 17 else None) if ro_sched else "no schedule"
+        ro_done: list[int] = []
+
+        def grow(a: int, n: int) -> None:
+            """``tr.grow(a, n)``, split at the scheduled reorders (a reorder runs between two grow calls)."""
+            nonlocal ro_off
+            b = a + n
+            for r in ([] if ro_off else [r for r in ro_sched if a <= r < b]):
+                tr.grow(a, r + 1 - a)
+                a = r + 1
+                if tr.reorder(r):
+                    ro_done.append(r)
+                else:
+                    ro_off = "not supported for this fit by the native trainer"
+                    break
+            if b > a:
+                tr.grow(a, b - a)
         tp = rep.mark("trainer_setup", tp, dev)
         completed = False
         try:
@@ -920,10 +976,10 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
                 # fetch + conversion leaves the fit's critical path.
                 tail = min(32, (T - T0) // 4)
                 head = T - tail
-                tr.grow(T0, head - T0)
+                grow(T0, head - T0)
                 ev = torch.cuda.Event()
                 ev.record()
-                tr.grow(head, T - head)
+                grow(head, T - head)
                 rep.extra["plan"] = tr.plan()
                 if world > 1:
                     _watch_segment(dist, dev, T0, head, tr, ev)
@@ -933,7 +989,7 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
             for s0 in ([head] if head is not None else range(T0, T, seg)):
                 s1 = min(T, s0 + seg)
                 if head is None:
-                    tr.grow(s0, s1 - s0)
+                    grow(s0, s1 - s0)
                     rep.extra["plan"] = tr.plan()
                 if world > 1:  # fail fast (abort the communicator) if a peer rank dies mid-segment
                     _watch_segment(dist, dev, s0, s1, tr)
@@ -947,6 +1003,8 @@ def train_binned(bd: BinnedData, y, params: GBDTParams | dict | None = None, *, 
                 tp = rep.mark("convert", tp, dev)
                 if early_stop(s0):  # (every grown tree was fetched: the context can be parked)
                     break
+            tr.unpermute()  # (reordered rows: the margins back in the caller's row order)
+            rep.extra["row_reorder"] = {"trees": ro_done, "off": ro_off}
             completed = True
         finally:
             tr.close(park=completed)  # a completed fit's context is kept for the next fit of these shapes

@@ -263,6 +263,21 @@ class GpuGbdtTrainer:
             raise RuntimeError(f"cobalt_gbdt_grow failed ({rc}): {self.lib.cobalt_comm_last_error().decode()}")
         _native.check(rc, "cobalt_gbdt_grow")
 
+    def reorder(self, tree: int) -> bool:
+        """Between two :meth:`grow` calls: regroup the rows by the leaf they reached in the grown tree
+        ``tree`` (csrc/gbdt.hip cobalt_gbdt_reorder; the next trees' node gathers then read runs of
+        consecutive rows). The model does not change. False where it does not apply (nothing done)."""
+        rc = self.lib.cobalt_gbdt_reorder(self.h, int(tree), _native.stream_handle())
+        if rc == 1:
+            return False
+        _native.check(rc, "cobalt_gbdt_reorder")
+        return True
+
+    def unpermute(self) -> None:
+        """After the last :meth:`grow` of a reordered fit: the margins back into the caller's tensor in
+        the original row order (a no-op when the rows were never reordered)."""
+        _native.check(self.lib.cobalt_gbdt_unpermute(self.h, _native.stream_handle()), "cobalt_gbdt_unpermute")
+
     # -------------------------------------------------------------- external-memory (sampled) mode
     def set_rows(self, n: int) -> None:
         """Rows of the current sample written into the bound records (<= the created capacity)."""
