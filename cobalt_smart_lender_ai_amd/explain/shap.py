@@ -212,3 +212,41 @@ def pd_plot(result: dict, ice: bool = True, max_ice: int = 200, centered: bool =
     ax.set_ylabel("partial dependence" + (" (centered)" if centered else ""))
     fig.tight_layout()
     return fig
+
+
+# ----------------------------------------------------------------------- permutation importance
+def permutation_importance(model, X, y, features=None, **kw) -> dict:
+    """Permutation feature importance (:meth:`Booster.permutation_importance`) of a ``GBDTClassifier``, a
+    ``Booster`` or a :class:`TreeExplainer`. A classifier scores the trees ``predict_proba`` scores (the first
+    ``best_iteration + 1`` of an early-stopped fit, or ``iteration_range=(0, n)``), on its device, and a
+    DataFrame's columns are reordered by feature name."""
+    if isinstance(model, TreeExplainer):
+        kw.setdefault("device", model.device)
+        return model.booster.permutation_importance(X, y, features, **kw)
+    if isinstance(model, Booster):
+        return model.permutation_importance(X, y, features, **kw)
+    if hasattr(model, "get_booster") and hasattr(model, "_n_trees"):
+        if "n_trees" in kw and "iteration_range" in kw:
+            raise ValueError("pass n_trees or iteration_range, not both")
+        if "n_trees" not in kw:
+            kw["n_trees"] = model._n_trees(kw.pop("iteration_range", None))
+        kw.setdefault("device", model.device)
+        return model.get_booster().permutation_importance(model._matrix(X), y, features, **kw)
+    raise TypeError("expected a GBDTClassifier, a Booster or a TreeExplainer")
+
+
+def importance_plot(result: dict, max_display: int = 10):
+    """Draw a :func:`permutation_importance` result: one horizontal box plot of the repeats per feature, the
+    ``max_display`` features with the largest mean importance, the largest on top."""
+    plt = _plt()
+    imp = np.asarray(result["importances"], np.float64)
+    mean = np.asarray(result["importances_mean"], np.float64)
+    order = np.argsort(-mean, kind="stable")[:max_display][::-1]
+    fig, ax = plt.subplots(figsize=(8, 0.4 * len(order) + 1.5))
+    if len(order):
+        ax.boxplot([imp[i] for i in order], vert=False)
+        ax.set_yticks(range(1, len(order) + 1), [result["feature_names"][i] for i in order])
+    ax.axvline(0, color="grey", lw=0.8)
+    ax.set_xlabel(f"permutation importance ({result['metric']} degradation)")
+    fig.tight_layout()
+    return fig

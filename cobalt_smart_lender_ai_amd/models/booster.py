@@ -359,6 +359,71 @@ class Booster:
             out["individual"] = sigmoid32(ind) if response == "probability" else ind
         return out
 
+    def permutation_importance(self, X, y, features=None, *, n_repeats: int = 5, metric: str = "logloss",
+                               sample_weight=None, random_state: int = 0, perm=None, n_trees: int | None = None,
+                               device: str | None = None) -> dict[str, Any]:
+        """Permutation feature importance (scikit-learn's ``permutation_importance``): how much ``metric`` on the
+        labelled rows ``(X, y)`` degrades when a feature's column is shuffled among the rows, everything else
+        as in ``X`` (which is not modified). Unlike the gain / cover counts it is measured on the rows given
+        here, held-out ones included.
+
+        ``features``: indices or names (default: every model feature). ``metric``: "logloss", "error" or "auc"
+        ("auc" is unweighted and refuses ``sample_weight``). ``perm``: int32 [R, N] row indices in [0, N), one
+        row per repeat; by default ``n_repeats`` permutations are drawn **once per call and shared by all
+        features** (:func:`draw_permutations`: ``n_repeats`` draws instead of ``len(features) * n_repeats``, and
+        the features are compared under common random numbers). A ``random_state`` is reproducible per device
+        and differs between CPU and GPU; pass ``perm`` where both must agree. ``n_trees``: score that prefix
+        of the forest.
+
+        Returns a dict shaped like scikit-learn's Bunch: ``importances`` float64 [n_features, R] = the
+        degradation, positive when the feature matters (``score - baseline`` for "logloss" / "error",
+        ``baseline - score`` for "auc"), ``importances_mean``, ``importances_std`` (ddof 0), ``baseline_score``,
+        ``scores`` [n_features, R], ``features`` (indices), ``feature_names``, ``metric``, ``n_repeats``. On a
+        GPU one pass of ``csrc/permimp.hip`` scores every (feature, repeat) job and the baseline; the sums are
+        reduced in a fixed order (same input, same bits), and a feature that no tree splits on has importance
+        exactly 0.0."""
+        from ..ops import predict_ops
+
+        if not isinstance(metric, str) or metric not in EVAL_METRICS:
+            raise ValueError(f"unknown metric {metric!r}: expected one of {EVAL_METRICS}")
+        names = self.feature_names or [f"f{i}" for i in range(self.num_feature)]
+        if features is None:
+            features = list(range(self.num_feature))
+        elif isinstance(features, (str, int, np.integer)):
+            features = [features]
+        feats = [self._feature_index(f) for f in features]
+        if hasattr(X, "columns") and self.feature_names:
+            X = X[self.feature_names]
+        if hasattr(X, "to_numpy"):
+            X = X.to_numpy(dtype=np.float32, na_value=np.nan)
+        if not hasattr(X, "shape") or len(X.shape) != 2:
+            X = np.asarray(X, dtype=np.float32)
+            if X.ndim != 2:
+                raise ValueError(f"X must be [rows, features], got shape {X.shape}")
+        N = int(X.shape[0])
+        if N == 0 or X.shape[1] < self.num_feature:
+            raise ValueError(f"X has shape {tuple(X.shape)}, model needs [rows >= 1, >= {self.num_feature}]")
+
+        def host_vec(v):
+            return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32).reshape(-1)
+
+        y32 = host_vec(y)
+        w32 = None if sample_weight is None else host_vec(sample_weight)
+        if perm is None and int(n_repeats) < 1:
+            raise ValueError(f"n_repeats must be at least 1, got {n_repeats}")
+        check_perm_inputs(N, y32, w32, (metric,), None if perm is None else tuple(perm.shape))
+        d = predict_ops._device_of(X, device)
+        if perm is None:
+            perm = draw_permutations(N, int(n_repeats), random_state, d if d.type == "cuda" else None)
+        base, scores = predict_ops.permutation_scores(self, X, y32, feats, perm, n_trees=n_trees, weights=w32,
+                                                      metrics=(metric,), device=d)
+        sc = np.asarray(scores[metric], dtype=np.float64)
+        imp = (base[metric] - sc) if EVAL_MAXIMIZE[metric] else (sc - base[metric])
+        return {"importances": imp, "importances_mean": imp.mean(axis=1) if len(feats) else np.zeros(0),
+                "importances_std": imp.std(axis=1) if len(feats) else np.zeros(0),
+                "baseline_score": float(base[metric]), "scores": sc, "features": feats,
+                "feature_names": [names[f] for f in feats], "metric": metric, "n_repeats": int(sc.shape[1])}
+
     def expected_value(self) -> float:
         """TreeExplainer ``expected_value``: base margin + cover-weighted mean leaf value per tree."""
         tot = 0.0
@@ -750,6 +815,97 @@ def partial_dependence_host(b: Booster, X: np.ndarray, feats: Sequence[int], gri
         avg_m[k] = math.fsum(wd * m) / sw
         avg_p[k] = math.fsum(wd * p) / sw
     return ice, avg_m, avg_p
+
+
+# ---------------------------------------------------------------------- permutation importance
+def draw_permutations(n_rows: int, n_repeats: int, random_state: int = 0, device=None):
+    """The ``n_repeats`` row permutations of one :meth:`Booster.permutation_importance` call, int32
+    [n_repeats, n_rows]. CPU: ``np.random.default_rng(random_state)`` and one ``rng.permutation`` per repeat
+    (a NumPy array). A CUDA ``device``: ``torch.randperm`` with a generator of that device seeded with
+    ``random_state``, one per repeat (a tensor on the device; nothing crosses the host). A seed is
+    reproducible per device and differs between the two."""
+    if int(n_repeats) < 1:
+        raise ValueError(f"n_repeats must be at least 1, got {n_repeats}")
+    if device is not None and str(device).startswith("cuda"):
+        import torch
+
+        gen = torch.Generator(device=device).manual_seed(int(random_state))
+        return torch.stack([torch.randperm(int(n_rows), generator=gen, dtype=torch.int32, device=device)
+                            for _ in range(int(n_repeats))])
+    rng = np.random.default_rng(random_state)
+    return np.stack([rng.permutation(int(n_rows)) for _ in range(int(n_repeats))]).astype(np.int32)
+
+
+def check_perm_inputs(n_rows: int, y: np.ndarray, w: np.ndarray | None, metrics: Sequence[str],
+                      perm_shape: tuple | None = None) -> tuple[str, ...]:
+    """The input checks of permutation importance beyond the contents of ``perm`` (host arrays; raised before
+    anything is computed or launched): those of :func:`check_eval_inputs`, "auc" with weights, and the shape
+    of ``perm`` ([R >= 1, n_rows])."""
+    metrics = check_eval_inputs(n_rows, y, w, metrics)
+    if "auc" in metrics and w is not None:
+        raise ValueError("the 'auc' metric is unweighted: pass sample_weight or metric='auc', not both")
+    if perm_shape is not None and (len(perm_shape) != 2 or perm_shape[0] < 1 or perm_shape[1] != n_rows):
+        raise ValueError(f"perm must be int32 [R >= 1, {n_rows}], got shape {tuple(perm_shape)}")
+    return metrics
+
+
+def metric_terms_host(margin: np.ndarray, y32: np.ndarray, w32: np.ndarray | None,
+                      metrics: Sequence[str]) -> dict[str, float]:
+    """The metrics of one job from its fp32 margins, as ``csrc/evalcurve.hip`` defines them (float64 terms
+    from the float32 margin; exact ``math.fsum`` sums)."""
+    out: dict[str, float] = {}
+    m = margin.astype(np.float64)
+    wd = np.ones(m.shape[0], dtype=np.float64) if w32 is None else w32.astype(np.float64)
+    sw = math.fsum(wd)
+    ypos = y32 > np.float32(0.5)
+    if "logloss" in metrics:
+        out["logloss"] = math.fsum(wd * (np.log1p(np.exp(-np.abs(m))) + np.maximum(m, 0.0)
+                                         - y32.astype(np.float64) * m)) / sw
+    if "error" in metrics:
+        out["error"] = math.fsum(wd * ((margin > 0) != ypos)) / sw
+    if "auc" in metrics:
+        from ..metrics.auc import roc_auc
+
+        out["auc"] = float(roc_auc(ypos.astype(np.float64), margin))
+    return out
+
+
+def permutation_scores_host(b: Booster, X: np.ndarray, y, feats: Sequence[int], perm: np.ndarray,
+                            n_trees: int | None = None, sample_weight=None,
+                            metrics: Sequence[str] = ("logloss",)) -> tuple[dict[str, float], dict[str, np.ndarray]]:
+    """The definition of the permutation-importance scores (CPU path and oracle of ``csrc/permimp.hip``): job
+    ``(i, r)`` scores a copy of ``X`` whose column ``feats[i]`` is ``X[perm[r], feats[i]]`` with
+    :func:`predict_margin_host`; the baseline scores ``X`` itself. NaN is swapped in like any value.
+    Returns ``(baseline, scores)``: ``{metric: float}`` and ``{metric: float64 [len(feats), R]}`` with
+    ``logloss = sum w (log1p(exp(-|m|)) + max(m, 0) - y m) / sum w`` and ``error = sum w [(m > 0) != (y > 0.5)]
+    / sum w`` in float64 from the float32 margin ``m``, and ``auc`` = :func:`~..metrics.auc.roc_auc` of
+    ``(y > 0.5, m)`` (unweighted). ``ValueError`` for a ``perm`` that is not [R >= 1, N] with entries in
+    [0, N), "auc" with weights or with one class, an unknown metric, and row-count mismatches. ``X`` is not
+    modified."""
+    X = np.asarray(X, dtype=np.float32)
+    N = X.shape[0]
+    y32 = np.asarray(y, dtype=np.float32).reshape(-1)
+    w32 = None if sample_weight is None else np.asarray(sample_weight, dtype=np.float32).reshape(-1)
+    perm = np.asarray(perm)
+    metrics = check_perm_inputs(N, y32, w32, metrics, perm.shape)
+    if perm.dtype.kind not in "iu" or int(perm.min()) < 0 or int(perm.max()) >= N:
+        raise ValueError(f"perm must hold integer row indices in [0, {N})")
+    feats = [int(f) for f in feats]
+    for f in feats:
+        if not 0 <= f < b.num_feature:
+            raise ValueError(f"feature index {f} outside [0, {b.num_feature})")
+    R = perm.shape[0]
+    base = metric_terms_host(predict_margin_host(b, X, n_trees), y32, w32, metrics)
+    scores = {m: np.empty((len(feats), R), dtype=np.float64) for m in metrics}
+    Xs = X.copy()
+    for i, f in enumerate(feats):
+        for r in range(R):
+            Xs[:, f] = X[perm[r], f]
+            got = metric_terms_host(predict_margin_host(b, Xs, n_trees), y32, w32, metrics)
+            for m in metrics:
+                scores[m][i, r] = got[m]
+        Xs[:, f] = X[:, f]
+    return base, scores
 
 
 def pd_grid_axis(col: np.ndarray, grid_resolution: int, percentiles: tuple[float, float]) -> np.ndarray:

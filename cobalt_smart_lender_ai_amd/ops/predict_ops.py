@@ -2,7 +2,7 @@
 :class:`Booster`.
 
 GPU path: gfx950 kernels in ``csrc/predict.hip`` (forest packed once per booster and device, cached),
-``csrc/shapint.hip``, ``csrc/evalcurve.hip`` and ``csrc/pdp.hip``.
+``csrc/shapint.hip``, ``csrc/evalcurve.hip``, ``csrc/pdp.hip`` and ``csrc/permimp.hip``.
 CPU path: the NumPy reference implementations in ``models/booster.py``.
 """
 from __future__ import annotations
@@ -15,9 +15,9 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..models.booster import (Booster, Tree, check_eval_inputs, eval_curve_host, partial_dependence_host,
-                              predict_margin_host, sigmoid32, staged_margins_host, treeshap_host,
-                              treeshap_interactions_host)
+from ..models.booster import (Booster, Tree, check_eval_inputs, check_perm_inputs, eval_curve_host,
+                              partial_dependence_host, permutation_scores_host, predict_margin_host, sigmoid32,
+                              staged_margins_host, treeshap_host, treeshap_interactions_host)
 from ..config import knob
 
 # LDS tile capacity in nodes: a model's tile is max(this, its largest tree), at most MAX_TILE_NODES
@@ -87,6 +87,18 @@ _native.register("cobalt_pdp_grid_chunk", ctypes.c_int, [])
 _native.register("cobalt_pdp_chunk_rows", ctypes.c_int64, [])
 _native.register("cobalt_pdp_max_grid", ctypes.c_int, [])
 PDP_MAX_GRID = 1 << 16         # grid points per call (csrc/pdp.hip kPdpMaxGrid)
+
+# csrc/permimp.hip: (X, n, F, ldx, nodes, tree_ptr, tile_ptr, n_tiles, tile_cap, base_margin, feats, nf, cols, perm,
+# R, y, w, margins, workspace, sums, rep_chunk, stream)
+_native.register("cobalt_perm_importance", ctypes.c_int,
+                 [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_int,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
+_native.register("cobalt_perm_workspace", ctypes.c_int64, [ctypes.c_int64, ctypes.c_int])
+_native.register("cobalt_perm_rep_chunk", ctypes.c_int, [])
+_native.register("cobalt_perm_chunk_rows", ctypes.c_int64, [])
+PERM_REP_CHUNK = 0             # repeats per block of csrc/permimp.hip: 0 = its default, 8 or 16 (sweeps)
 
 PATH_ELEM = np.dtype([("lo", "<f4"), ("hi", "<f4"), ("feat", "<i4"), ("nan_ok", "<i4"), ("zero", "<f8")])
 
@@ -558,6 +570,130 @@ def partial_dependence(b: Booster, X, feats, grids, *, n_trees: int | None = Non
         s = sums.cpu().numpy()
         am, ap = s[0:-1:2] / s[-1], s[1:-1:2] / s[-1]
     return (None if ice is None else ice.cpu().numpy()), am, ap
+
+
+# ------------------------------------------------------------------------ permutation importance
+def permutation_scores_gpu(b: Booster, X: torch.Tensor, y: torch.Tensor | None, feats, perm: torch.Tensor, *,
+                           n_trees: int | None = None, weights: torch.Tensor | None = None, want_margins: bool,
+                           want_sums: bool) -> tuple[torch.Tensor | None, torch.Tensor | None]:
+    """Launch ``csrc/permimp.hip`` on the current stream. Job 0 scores ``X`` (the baseline), job
+    ``1 + i * R + r`` scores every row ``n`` with ``x[feats[i]] = X[perm[r][n], feats[i]]``; ``X`` is not written.
+    Returns ``(margins, sums)``: ``margins`` [1 + nf R, N] float32 with the bits of ``predict_margin`` on the
+    substituted matrix (``want_margins``), ``sums`` [2 (1 + nf R) + 1] float64 = (sum w loss, sum w err) per
+    job, then sum w (``want_sums``; deterministic: fixed reduction order, no floating-point atomics).
+    ``X`` as for :func:`predict_gpu`; ``y`` (needed for the sums) and ``weights``: contiguous float32 [N] on the
+    device of ``X``; ``perm``: contiguous int32 [R, N] on that device. The kernel reads
+    ``cols[i][perm[r][n]]`` unchecked, so the range of ``perm`` is checked here, on the device (two
+    reductions and the one host read of this function). ``ValueError`` / ``RuntimeError`` (a model outside
+    the kernel's LDS limits) before anything of the kernel is launched."""
+    _check_kernel_rows(b, X)
+    N, F = X.shape
+    feats = [int(f) for f in feats]
+    for f in feats:
+        if not 0 <= f < b.num_feature:
+            raise ValueError(f"feature index {f} outside [0, {b.num_feature})")
+    nf = len(feats)
+    if (not isinstance(perm, torch.Tensor) or perm.dtype != torch.int32 or perm.dim() != 2 or perm.shape[0] < 1
+            or perm.shape[1] != N or perm.device != X.device or not perm.is_contiguous()):
+        raise ValueError(f"perm must be a contiguous int32 [R >= 1, {N}] tensor on {X.device}")
+    R = int(perm.shape[0])
+    for name, v in (("y", y), ("weights", weights)):
+        if v is not None and (v.dtype != torch.float32 or v.dim() != 1 or v.shape[0] != N or v.device != X.device
+                              or not v.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 [{N}] tensor on {X.device}")
+    if want_sums and y is None:
+        raise ValueError("the sums need y")
+    if N == 0:
+        raise ValueError("X has no rows")
+    lo, hi = (int(v) for v in torch.stack([perm.min(), perm.max()]).tolist())
+    if lo < 0 or hi >= N:
+        raise ValueError(f"perm must hold row indices in [0, {N}), got [{lo}, {hi}]")
+    J = 1 + nf * R
+    gf = gpu_forest(b, X.device, n_trees)
+    lib = _native.lib()
+    ft = torch.tensor(feats, dtype=torch.int32, device=X.device) if nf else None
+    cols = X[:, feats].t().contiguous() if nf else None   # [nf, N]: the gather reads 4 N contiguous bytes
+    margins = torch.empty((J, N), dtype=torch.float32, device=X.device) if want_margins else None
+    sums = work = None
+    if want_sums:
+        sums = torch.zeros(2 * J + 1, dtype=torch.float64, device=X.device)
+        work = torch.empty(int(lib.cobalt_perm_workspace(N, J)), dtype=torch.uint8, device=X.device)
+    rc = lib.cobalt_perm_importance(X.data_ptr(), N, F, X.stride(0), gf.nodes.data_ptr(), gf.tree_ptr.data_ptr(),
+                                    gf.tile_ptr.data_ptr(), gf.n_tiles, gf.tile_cap, b.base_margin, _native.ptr(ft),
+                                    nf, _native.ptr(cols), perm.data_ptr(), R, _native.ptr(y) if want_sums else None,
+                                    _native.ptr(weights), _native.ptr(margins), _native.ptr(work),
+                                    _native.ptr(sums), PERM_REP_CHUNK, _native.stream_handle())
+    _native.check(rc, "cobalt_perm_importance")
+    return margins, sums
+
+
+def permutation_scores(b: Booster, X, y, feats, perm, *, n_trees: int | None = None, weights=None,
+                       metrics=("logloss",), device=None) -> tuple[dict[str, float], dict[str, np.ndarray]]:
+    """``(baseline, scores)``: ``{metric: float}`` of ``(X, y)`` and ``{metric: float64 [len(feats), R]}`` of
+    the jobs (feature ``feats[i]`` shuffled by ``perm[r]``). A CUDA device runs ``csrc/permimp.hip``: "logloss"
+    and "error" come from one launch that never materialises margins; "auc" stages the margins of at most
+    ``AUC_STAGE_BYTES`` of jobs at a time and scores each with :func:`~..metrics.auc.roc_auc`, as
+    :func:`eval_curve` does. The CPU runs :func:`~..models.booster.permutation_scores_host` (the definition).
+    ``ValueError`` as there, before any launch."""
+    d = _device_of(X, device)
+    y32 = _host_vec(y)
+    w32 = None if weights is None else _host_vec(weights)
+    if d.type != "cuda":
+        Xn = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
+        pn = perm.cpu().numpy() if isinstance(perm, torch.Tensor) else np.asarray(perm)
+        return permutation_scores_host(b, Xn, y32, feats, pn, n_trees, w32, metrics)
+    Xt = _as_f32(X, d)
+    N = Xt.shape[0]
+    pshape = tuple(perm.shape) if hasattr(perm, "shape") else np.asarray(perm).shape
+    metrics = check_perm_inputs(N, y32, w32, metrics, pshape)
+    if isinstance(perm, torch.Tensor):
+        if perm.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+            raise ValueError("perm must hold integer row indices")
+        if perm.dtype != torch.int32 and (int(perm.min()) < 0 or int(perm.max()) >= N):
+            raise ValueError(f"perm must hold row indices in [0, {N})")
+        pt = perm.to(device=d, dtype=torch.int32).contiguous()
+    else:
+        pn = np.asarray(perm)
+        if pn.dtype.kind not in "iu" or int(pn.min()) < 0 or int(pn.max()) >= N:
+            raise ValueError(f"perm must hold integer row indices in [0, {N})")
+        pt = torch.as_tensor(np.ascontiguousarray(pn, dtype=np.int32), device=d)
+    feats = [int(f) for f in feats]
+    nf, R = len(feats), int(pt.shape[0])
+    yt = torch.as_tensor(y32, device=d)
+    wt = None if w32 is None else torch.as_tensor(w32, device=d)
+    base: dict[str, float] = {}
+    scores: dict[str, np.ndarray] = {}
+    if "logloss" in metrics or "error" in metrics:
+        _, sums = permutation_scores_gpu(b, Xt, yt, feats, pt, n_trees=n_trees, weights=wt, want_margins=False,
+                                         want_sums=True)
+        s = sums.cpu().numpy()
+        for k, name in enumerate(("logloss", "error")):
+            if name in metrics:
+                v = s[k:-1:2] / s[-1]
+                base[name] = float(v[0])
+                scores[name] = v[1:].reshape(nf, R).copy()
+    if "auc" in metrics:
+        from ..metrics.auc import roc_auc
+
+        ypos = (yt > 0.5).to(torch.float64)
+        auc = np.empty((nf, R), dtype=np.float64)
+        per = max(1, AUC_STAGE_BYTES // max(4 * N, 1) - 1)  # jobs per launch next to its baseline
+        have_base = False
+        if per >= R:  # whole features: per // R of them at a time
+            groups = [(feats[i:i + per // R], i, 0, R) for i in range(0, nf, per // R)]
+        else:         # one feature at a time, `per` of its repeats
+            groups = [([feats[i]], i, r0, min(R, r0 + per)) for i in range(nf) for r0 in range(0, R, per)]
+        for fs, i0, r0, r1 in groups or [([], 0, 0, R)]:
+            m, _ = permutation_scores_gpu(b, Xt, None, fs, pt[r0:r1], n_trees=n_trees, want_margins=True,
+                                          want_sums=False)
+            if not have_base:
+                base["auc"] = float(roc_auc(ypos, m[0]))
+                have_base = True
+            for i in range(len(fs)):
+                for r in range(r1 - r0):
+                    auc[i0 + i, r0 + r] = roc_auc(ypos, m[1 + i * (r1 - r0) + r])
+        scores["auc"] = auc
+    return {m: base[m] for m in metrics}, {m: scores[m] for m in metrics}
 
 
 def shap_values(b: Booster, X, device=None):

@@ -41,12 +41,21 @@ class RFEResult:
 
 def rfe(X, y, params: gbdt.GBDTParams | dict, n_features_to_select: int = 20, step: int = 1,
         device=None, feature_names: list[str] | None = None, importance_type: str = "gain",
-        binned: gbdt.BinnedData | None = None, step_score=None, repack: bool = True) -> RFEResult:
+        binned: gbdt.BinnedData | None = None, step_score=None, repack: bool = True,
+        perm_kwargs: dict | None = None) -> RFEResult:
     """``step_score(booster, support)`` (optional) is called for every fitted subset, from all
     features down to the final one -- the hook RFECV scores the elimination path with.
-    ``repack=False``: masked fits on the full-width matrix (the same trees, at the full width's cost)."""
+    ``repack=False``: masked fits on the full-width matrix (the same trees, at the full width's cost).
+    ``importance_type="permutation"`` ranks the surviving features by the mean
+    :meth:`Booster.permutation_importance` on ``(X, y)`` instead of a gain / cover count of the trees (same
+    ``np.argsort`` elimination rule); ``perm_kwargs``: its ``n_repeats``, ``metric`` and ``random_state``."""
     if isinstance(params, dict):
         params = gbdt.GBDTParams.from_kwargs(**params)
+    perm_kwargs = dict(perm_kwargs or {})
+    if importance_type != "permutation" and perm_kwargs:
+        raise ValueError("perm_kwargs needs importance_type='permutation'")
+    if set(perm_kwargs) - {"n_repeats", "metric", "random_state"}:
+        raise ValueError(f"perm_kwargs takes n_repeats, metric and random_state, got {sorted(perm_kwargs)}")
     bd = binned if binned is not None else gbdt.bin_dataset(X, max_bin=params.max_bin,
                                                             sketch_rows=params.sketch_rows, device=device)
     F = bd.n_features
@@ -85,8 +94,12 @@ def rfe(X, y, params: gbdt.GBDTParams | dict, n_features_to_select: int = 20, st
         bst = fit(support)
         if step_score is not None:
             step_score(bst, support.copy())
-        imp_full = bst.feature_importances(importance_type)
-        imp = imp_full[feats]
+        if importance_type == "permutation":
+            imp = bst.permutation_importance(X, y, features=[int(f) for f in feats], device=bd.device,
+                                             **perm_kwargs)["importances_mean"]
+        else:
+            imp_full = bst.feature_importances(importance_type)
+            imp = imp_full[feats]
         ranks = np.argsort(imp)
         thr = min(step, int(support.sum()) - n_features_to_select)
         drop = feats[ranks][:thr]
