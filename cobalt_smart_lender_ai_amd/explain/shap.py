@@ -3,7 +3,8 @@ src/api/cobalt_fast_api.py:46,100 and notebooks/04_model_training.ipynb cells 24
 
 ``TreeExplainer(model).shap_values(X)`` returns path-dependent (``feature_perturbation=
 "tree_path_dependent"``) SHAP values in margin space, ``expected_value`` is the cover-weighted mean
-leaf sum (the API's ``base_value``). ``shap`` itself is not a dependency: the summary / bar /
+leaf sum (the API's ``base_value``). ``TreeExplainer(model, data=Z)`` returns interventional values
+against the background rows ``Z``, optionally in probability space. ``shap`` itself is not a dependency: the summary / bar /
 waterfall / force views the notebook draws are produced with matplotlib from the same arrays.
 """
 from __future__ import annotations
@@ -21,14 +22,61 @@ def _booster(model) -> Booster:
     raise TypeError("expected a Booster or a fitted GBDTClassifier")
 
 
+FEATURE_PERTURBATIONS = ("auto", "interventional", "tree_path_dependent")
+
+
 class TreeExplainer:
-    def __init__(self, model, device=None):
+    """``shap.TreeExplainer(model, data=None, feature_perturbation="auto", model_output="raw")``.
+
+    Without ``data``: path-dependent values in margin space, ``expected_value`` = the cover-weighted mean
+    leaf sum. With ``data`` (a background set, [B, F]): interventional values against its rows, in margin
+    space or, with ``model_output="probability"``, in probability space; ``expected_value`` = the mean margin /
+    probability of the background rows. ``shap``'s rules for the combinations: "interventional" needs ``data``,
+    "tree_path_dependent" does not take it, and "probability" needs the interventional values."""
+
+    def __init__(self, model, data=None, feature_perturbation="auto", model_output="raw", device=None):
         self.booster = _booster(model)
         self.device = device
-        self.expected_value = float(self.booster.expected_value())
         self.feature_names = list(self.booster.feature_names or [f"f{i}" for i in range(self.booster.num_feature)])
+        if feature_perturbation not in FEATURE_PERTURBATIONS:
+            raise ValueError(f"feature_perturbation must be one of {FEATURE_PERTURBATIONS}, "
+                             f"got {feature_perturbation!r}")
+        if model_output not in ("raw", "probability"):
+            raise ValueError(f"model_output must be 'raw' or 'probability', got {model_output!r}")
+        if data is None:
+            if feature_perturbation == "interventional":
+                raise ValueError("feature_perturbation='interventional' needs a background set: pass data=")
+            if model_output == "probability":
+                raise ValueError("model_output='probability' needs interventional values against a background "
+                                 "set (pass data=): the path-dependent values exist in margin space only")
+            feature_perturbation = "tree_path_dependent"
+        elif feature_perturbation == "tree_path_dependent":
+            raise ValueError("feature_perturbation='tree_path_dependent' takes its baseline from the covers stored "
+                             "in the trees and cannot use data=; drop data= or ask for 'interventional'")
+        else:
+            feature_perturbation = "interventional"
+        self.feature_perturbation = feature_perturbation
+        self.model_output = model_output
+        self.data = None if data is None else self._matrix(data)
+        if self.data is None:
+            self.expected_value = float(self.booster.expected_value())
+        else:
+            self.expected_value = float(self.booster.expected_value_interventional(self.data, model_output))
+
+    def _matrix(self, X) -> np.ndarray:
+        """``X`` as a float32 array; a DataFrame's columns are reordered by feature name."""
+        names = self.booster.feature_names
+        if hasattr(X, "columns") and names:
+            X = X[names]
+        if hasattr(X, "to_numpy"):
+            return X.to_numpy(dtype=np.float32, na_value=np.nan)
+        return np.asarray(X.detach().cpu().numpy() if hasattr(X, "detach") else X, np.float32)
 
     def shap_values(self, X) -> np.ndarray:
+        if self.data is not None:
+            phi = self.booster.shap_values_interventional(self._matrix(X), self.data, model_output=self.model_output,
+                                                          device=self.device)
+            return np.asarray(phi.cpu().numpy() if hasattr(phi, "cpu") else phi, dtype=np.float64)
         names = self.booster.feature_names
         if hasattr(X, "columns") and names:
             X = X[names]
@@ -38,7 +86,9 @@ class TreeExplainer:
 
     def shap_interaction_values(self, X) -> np.ndarray:
         """``shap.TreeExplainer.shap_interaction_values``: [N, F, F] float64; a DataFrame's columns are
-        reordered by feature name."""
+        reordered by feature name. Path-dependent only."""
+        if self.data is not None:
+            raise ValueError("interaction values are path-dependent only: build the explainer without data=")
         names = self.booster.feature_names
         if hasattr(X, "columns") and names:
             X = X[names]

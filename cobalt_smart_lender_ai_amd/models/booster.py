@@ -257,6 +257,27 @@ class Booster:
 
         return predict_ops.shap_interaction_values(self, X, device=device)
 
+    def shap_values_interventional(self, X, background, *, model_output: str = "raw", n_trees: int | None = None,
+                                   device: str | None = None):
+        """Interventional TreeSHAP values [N, F] float64 of ``X`` against the rows of ``background``
+        (``shap``'s ``feature_perturbation="interventional"``): the mean over the background rows z of the
+        Shapley values of ``S -> f(x on S, z elsewhere)``; covers are not used. ``model_output``: "raw"
+        (margin) or "probability" (``shap``'s per-pair rescaling); with
+        :meth:`expected_value_interventional` the values of a row add up to its margin / probability.
+        ``n_trees``: explain the first trees only."""
+        from ..ops import predict_ops
+
+        return predict_ops.shap_values_interventional(self, X, background, model_output=model_output,
+                                                      n_trees=n_trees, device=device)
+
+    def expected_value_interventional(self, background, model_output: str = "raw",
+                                      n_trees: int | None = None) -> float:
+        """The baseline of :meth:`shap_values_interventional`: the mean over the background rows of the
+        float64 margin ("raw") or of its sigmoid ("probability")."""
+        Z = background.detach().cpu().numpy() if hasattr(background, "detach") else np.asarray(background)
+        b = self if n_trees is None else self.slice(n_trees)
+        return expected_value_interventional_host(b, Z.astype(np.float32, copy=False), model_output)
+
     def _feature_index(self, f) -> int:
         """A feature given by index or by name (``feature_names``) as an index; ``ValueError`` otherwise."""
         if isinstance(f, str):
@@ -1177,6 +1198,158 @@ def shapley_interactions_bruteforce(b: Booster, X: np.ndarray) -> np.ndarray:
                         out[n, i, j] += wgt * (fx[S | {i, j}] - fx[S | {i}] - fx[S | {j}] + fx[S])
         for i in range(F):
             out[n, i, i] = phi[i] - (out[n, i].sum() - out[n, i, i])
+    return out
+
+
+# ----------------------------------------------------------------- interventional TreeSHAP
+MODEL_OUTPUTS = ("raw", "probability")
+SHAP_MAX_UNIQUE = 15    # unique features on a path the interventional weight table covers
+
+
+def check_model_output(model_output: str) -> bool:
+    """True for "probability", False for "raw"; ``ValueError`` otherwise."""
+    if model_output not in MODEL_OUTPUTS:
+        raise ValueError(f"model_output must be one of {MODEL_OUTPUTS}, got {model_output!r}")
+    return model_output == "probability"
+
+
+def predict_margin64_host(b: Booster, X: np.ndarray) -> np.ndarray:
+    """The margin as the SHAP values see it: ``base_margin`` plus the leaf values in tree order, summed in
+    float64 (the predictor sums the same leaves in float32)."""
+    X = np.asarray(X, dtype=np.float32)
+    N = X.shape[0]
+    out = np.full(N, np.float64(b.base_margin), dtype=np.float64)
+    rows = np.arange(N)
+    for t in b.trees:
+        nid = np.zeros(N, dtype=np.int32)
+        while True:
+            lc = t.left_children[nid]
+            active = lc != -1
+            if not active.any():
+                break
+            v = X[rows, np.where(active, t.split_indices[nid], 0)]
+            go_left = np.where(np.isnan(v), t.default_left[nid] == 1, v < t.split_conditions[nid])
+            nid = np.where(active, np.where(go_left, lc, t.right_children[nid]), nid)
+        out = out + t.split_conditions[nid].astype(np.float64)
+    return out
+
+
+def sigmoid64(m) -> np.ndarray:
+    m = np.asarray(m, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        return 1.0 / (1.0 + np.exp(-m))
+
+
+def probability_rescale(fx, fz) -> np.ndarray:
+    """``(sigmoid(fx) - sigmoid(fz)) / (fx - fz)``, broadcast; where ``fx == fz`` the derivative
+    ``sigmoid'(fx)``. Evaluated as ``sigmoid(hi) sigmoid(-lo) (1 - exp(-d)) / d`` with ``d = hi - lo``: the
+    same function without the cancellation of the quotient at nearly equal margins."""
+    fx, fz = np.broadcast_arrays(np.asarray(fx, np.float64), np.asarray(fz, np.float64))
+    hi, lo = np.maximum(fx, fz), np.minimum(fx, fz)
+    d = hi - lo
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(d == 0.0, 1.0, -np.expm1(-d) / d)
+    return sigmoid64(hi) * sigmoid64(-lo) * r
+
+
+def interventional_weights() -> np.ndarray:
+    """``W[a, b] = (a - 1)! b! / (a + b)!`` for ``a >= 1``, ``a + b <= SHAP_MAX_UNIQUE`` (0 elsewhere): the
+    Shapley weight of each of ``a`` features only the explained row satisfies, next to ``b`` only the
+    background row satisfies; the weight of each of those ``b`` is ``-W[b, a]``."""
+    n = SHAP_MAX_UNIQUE + 1
+    W = np.zeros((n, n), dtype=np.float64)
+    for a in range(1, n):
+        for c in range(n - a):
+            W[a, c] = math.factorial(a - 1) * math.factorial(c) / math.factorial(a + c)
+    return W
+
+
+def check_background(b: Booster, X: np.ndarray, Z: np.ndarray) -> None:
+    if X.ndim != 2 or X.shape[1] < b.num_feature:
+        raise ValueError(f"X has shape {X.shape}, model needs [rows, >= {b.num_feature}]")
+    if Z.ndim != 2 or Z.shape[1] < b.num_feature:
+        raise ValueError(f"the background has shape {Z.shape}, model needs [rows, >= {b.num_feature}]")
+    if Z.shape[0] == 0:
+        raise ValueError("the background set has no rows")
+
+
+def treeshap_interventional_host(b: Booster, X: np.ndarray, Z: np.ndarray, model_output: str = "raw") -> np.ndarray:
+    """Interventional TreeSHAP values [N, F] float64 of the rows ``X`` against the background rows ``Z``
+    (``shap.TreeExplainer(model, data, feature_perturbation="interventional")``); CPU path of
+    :meth:`Booster.shap_values_interventional` and oracle of the GPU kernel. Covers are not used.
+
+    For a pair (x, z) the game is ``v(S) = f(x on S, z elsewhere)``. Per merged leaf path with leaf value
+    ``v``: a feature neither row satisfies kills the path; otherwise with ``a`` features only x satisfies and
+    ``c`` only z satisfies, each x-only feature gets ``+v (a-1)! c! / (a+c)!`` and each z-only feature
+    ``-v a! (c-1)! / (a+c)!``. "raw": the mean over the background. "probability": every pair is scaled by
+    :func:`probability_rescale` of the float64 margins (:func:`predict_margin64_host`) before the mean.
+    Vectorised over rows, background rows and the paths of equal length."""
+    prob = check_model_output(model_output)
+    X = np.asarray(X, dtype=np.float32)
+    Z = np.asarray(Z, dtype=np.float32)
+    check_background(b, X, Z)
+    N, F = X.shape
+    nB = Z.shape[0]
+    phi = np.zeros((N, F), dtype=np.float64)
+    if N == 0:
+        return phi
+    groups = _paths_by_length(b)
+    if groups and groups[-1][0] > SHAP_MAX_UNIQUE:
+        raise ValueError(f"path with {groups[-1][0]} unique features exceeds the TreeSHAP limit {SHAP_MAX_UNIQUE}")
+    W = interventional_weights()
+    scale = probability_rescale(predict_margin64_host(b, X)[:, None], predict_margin64_host(b, Z)[None, :]) \
+        if prob else None                                                         # [N, B]
+    for k, (v, feat, lo, hi, nan_ok, _zero) in groups:
+        P = len(v)
+        zv = Z[:, feat]                                                           # [B, P, k]
+        zs = np.where(np.isnan(zv), nan_ok, (zv >= lo) & ~(zv >= hi))
+        step = max(1, (1 << 23) // max(nB * P * k, 1))                            # rows per block of pairs
+        for r0 in range(0, N, step):
+            xv = X[r0:r0 + step][:, feat]                                         # [n, P, k]
+            xs = np.where(np.isnan(xv), nan_ok, (xv >= lo) & ~(xv >= hi))[:, None]   # [n, 1, P, k]
+            x1, z1 = xs & ~zs[None], ~xs & zs[None]                               # [n, B, P, k]
+            ok = (xs | zs[None]).all(-1)
+            a, c = x1.sum(-1), z1.sum(-1)
+            wx = np.where(ok, W[a, c], 0.0)                                       # [n, B, P]
+            wz = np.where(ok, W[c, a], 0.0)
+            if prob:
+                wx = wx * scale[r0:r0 + step, :, None]
+                wz = wz * scale[r0:r0 + step, :, None]
+            val = v[None, :, None] * (x1 * wx[..., None] - z1 * wz[..., None]).sum(1)   # [n, P, k]
+            np.add.at(phi, (np.arange(r0, r0 + xv.shape[0])[:, None, None], feat[None]), val)
+    return phi / nB
+
+
+def expected_value_interventional_host(b: Booster, Z: np.ndarray, model_output: str = "raw") -> float:
+    """The baseline of :func:`treeshap_interventional_host`: the mean float64 margin of the background rows,
+    or the mean of their probabilities."""
+    prob = check_model_output(model_output)
+    Z = np.asarray(Z, dtype=np.float32)
+    check_background(b, Z, Z)
+    m = predict_margin64_host(b, Z)
+    return float(np.mean(sigmoid64(m) if prob else m))
+
+
+def shapley_interventional_bruteforce(b: Booster, X: np.ndarray, Z: np.ndarray) -> np.ndarray:
+    """Interventional Shapley values of every pair, [N, B, F] float64, by the definition, for tests on tiny
+    models (F <= 10): all 2^F hybrid rows (x on S, z elsewhere) are scored on the raw trees and
+    ``phi_i = sum_{S without i} |S|! (F - |S| - 1)! / F! (v(S + i) - v(S))``. No paths, no closed form."""
+    X = np.asarray(X, dtype=np.float32)
+    Z = np.asarray(Z, dtype=np.float32)
+    N, F = X.shape
+    if F > 10:
+        raise ValueError("brute-force interventional values are for F <= 10")
+    masks = np.arange(1 << F)
+    in_s = ((masks[:, None] >> np.arange(F)[None, :]) & 1).astype(bool)           # [2^F, F]
+    size = in_s.sum(1)
+    wgt = np.array([math.factorial(s) * math.factorial(F - s - 1) / math.factorial(F) for s in range(F)])
+    out = np.zeros((N, Z.shape[0], F), dtype=np.float64)
+    for n in range(N):
+        for j in range(Z.shape[0]):
+            v = predict_margin64_host(b, np.where(in_s, X[n][None, :], Z[j][None, :F]))
+            for i in range(F):
+                without = masks[~in_s[:, i]]
+                out[n, j, i] = ((v[without | (1 << i)] - v[without]) * wgt[size[without]]).sum()
     return out
 
 

@@ -2,7 +2,7 @@
 :class:`Booster`.
 
 GPU path: gfx950 kernels in ``csrc/predict.hip`` (forest packed once per booster and device, cached),
-``csrc/shapint.hip``, ``csrc/evalcurve.hip``, ``csrc/pdp.hip`` and ``csrc/permimp.hip``.
+``csrc/shapint.hip``, ``csrc/shapbg.hip``, ``csrc/evalcurve.hip``, ``csrc/pdp.hip`` and ``csrc/permimp.hip``.
 CPU path: the NumPy reference implementations in ``models/booster.py``.
 """
 from __future__ import annotations
@@ -15,9 +15,10 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..models.booster import (Booster, Tree, check_eval_inputs, check_perm_inputs, eval_curve_host,
-                              partial_dependence_host, permutation_scores_host, predict_margin_host, sigmoid32,
-                              staged_margins_host, treeshap_host, treeshap_interactions_host)
+from ..models.booster import (Booster, Tree, check_background, check_eval_inputs, check_model_output,
+                              check_perm_inputs, eval_curve_host, partial_dependence_host, permutation_scores_host,
+                              predict_margin_host, sigmoid32, staged_margins_host, treeshap_host,
+                              treeshap_interactions_host, treeshap_interventional_host)
 from ..config import knob
 
 # LDS tile capacity in nodes: a model's tile is max(this, its largest tree), at most MAX_TILE_NODES
@@ -65,6 +66,24 @@ SHAP_INT_MAX_F = 48            # widest model of the interaction kernel (csrc/sh
 # (phi [rows, F] plus treeshap_gpu's [rows, chunks, F] slab: 16384 x 117 x 20 doubles = 307 MB for the
 # shipped model); the interaction kernel itself keeps its accumulators in LDS and has no global scratch.
 SHAP_INT_ROWS = 16384
+
+# csrc/shapbg.hip: masks (X, n, F, ldx, elems, path_ptr, path_val, n_paths, max_len, base_margin, masks, margins,
+# stream); values (X, n, F, ldx, elems, path_ptr, path_val, n_paths, max_len, zmask, zmargin, nb, xmargin, first,
+# last, n_background, phi, stream)
+_native.register("cobalt_shapbg_masks", ctypes.c_int,
+                 [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p])
+_native.register("cobalt_treeshap_interventional", ctypes.c_int,
+                 [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p])
+_native.register("cobalt_shapbg_max_f", ctypes.c_int, [])
+_native.register("cobalt_shapbg_max_tile", ctypes.c_int, [])
+SHAP_BG_MAX_F = 256            # widest X of the interventional kernel (csrc/shapbg.hip kBgMaxF)
+SHAP_BG_MAX_TILE = 1024        # background rows per launch (csrc/shapbg.hip kBgMaxTile)
+SHAP_BG_MASK_BYTES = 64 << 20  # mask workspace: the background tile is this many bytes of [tile, n_paths] uint16
+SHAP_BG_ROWS = 16384           # rows of X per launch (bounds the margins of probability mode)
 
 # csrc/evalcurve.hip: (X, n, F, ldx, y, w, nodes, tree_ptr, tile_ptr, n_tiles, tile_cap, n_trees, base_margin,
 # margin_in, margin_out, stage_margins, workspace, sums, stream)
@@ -750,3 +769,100 @@ def shap_interaction_values(b: Booster, X, device=None):
         return out if isinstance(X, torch.Tensor) else out.cpu().numpy()
     Xn = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
     return treeshap_interactions_host(b, Xn)
+
+
+# ------------------------------------------------------------------------ interventional TreeSHAP
+_FORCE_BG_TILE = 0  # tests: background rows per tile (0 = from the model), so small sets span several tiles
+
+
+def _background_tile(n_paths: int) -> int:
+    """Background rows per launch: a function of the model alone, so a row's values do not depend on N."""
+    if _FORCE_BG_TILE:
+        return max(1, min(int(_FORCE_BG_TILE), SHAP_BG_MAX_TILE))
+    return max(1, min(SHAP_BG_MAX_TILE, SHAP_BG_MASK_BYTES // max(2 * n_paths, 1)))
+
+
+def _sliced(b: Booster, n_trees: int | None) -> Booster:
+    """The first ``n_trees`` trees as a booster, kept with ``b`` (its packed paths live on the object)."""
+    if n_trees is None or n_trees == b.num_trees:
+        return b
+    if not 0 <= n_trees <= b.num_trees:
+        raise ValueError(f"n_trees must be in [0, {b.num_trees}], got {n_trees}")
+    cache = b.__dict__.setdefault("_slice_cache", {})
+    ent = cache.get(n_trees)
+    if ent is None or len(ent.trees) != n_trees or any(x is not y for x, y in zip(ent.trees, b.trees)):
+        ent = cache[n_trees] = b.slice(n_trees)
+    return ent
+
+
+def treeshap_interventional_gpu(b: Booster, X: torch.Tensor, Z: torch.Tensor, phi: torch.Tensor, *,
+                                probability: bool = False) -> None:
+    """Write the interventional TreeSHAP values of the rows ``X`` against the background rows ``Z`` into
+    ``phi`` [N, F] float64 on the current stream (``csrc/shapbg.hip``; margin space, or ``shap``'s per-pair
+    rescaling to probability space). Deterministic: no floating-point atomics, and a row's values do not
+    depend on the batch. ``X`` and ``Z`` as for :func:`predict_gpu` (rows may be strided). The workspace is a
+    background tile of masks (``SHAP_BG_MASK_BYTES``) whatever N and B are. ``ValueError`` before anything is
+    launched for an empty background, more than ``MAX_PATH`` unique features on a path and more than
+    ``SHAP_BG_MAX_F`` columns."""
+    _check_kernel_rows(b, X)
+    _check_kernel_rows(b, Z)
+    N, F = X.shape
+    B, Fz = Z.shape
+    if B == 0:
+        raise ValueError("the background set has no rows")
+    if Z.device != X.device:
+        raise ValueError(f"X is on {X.device}, the background on {Z.device}")
+    if max(F, Fz) > SHAP_BG_MAX_F:
+        raise ValueError(f"{max(F, Fz)} columns exceed the GPU interventional TreeSHAP limit of {SHAP_BG_MAX_F}")
+    if tuple(phi.shape) != (N, F) or phi.dtype != torch.float64 or not phi.is_contiguous() or phi.device != X.device:
+        raise ValueError(f"phi must be a contiguous float64 [{N}, {F}] tensor on {X.device}")
+    gf = gpu_forest(b, X.device, None, with_shap=True)  # (raises ValueError past MAX_PATH features per path)
+    if N == 0:
+        return
+    lib = _native.lib()
+    stream = _native.stream_handle()
+    tile = _background_tile(gf.n_paths)
+    zmask = torch.empty(max(min(tile, B) * gf.n_paths, 1), dtype=torch.int16, device=X.device)
+    zmargin = torch.empty(min(tile, B), dtype=torch.float64, device=X.device)
+    paths = (_native.ptr(gf.elems), gf.path_ptr.data_ptr(), gf.path_val.data_ptr(), gf.n_paths, gf.max_len)
+    for r0 in range(0, N, SHAP_BG_ROWS):
+        Xr = X[r0:r0 + SHAP_BG_ROWS]
+        n = Xr.shape[0]
+        xmargin = None
+        if probability:
+            xmargin = torch.empty(n, dtype=torch.float64, device=X.device)
+            rc = lib.cobalt_shapbg_masks(Xr.data_ptr(), n, F, X.stride(0), *paths, float(b.base_margin), None,
+                                         xmargin.data_ptr(), stream)
+            _native.check(rc, "cobalt_shapbg_masks")
+        for t0 in range(0, B, tile):
+            Zt = Z[t0:t0 + tile]
+            nb = Zt.shape[0]
+            rc = lib.cobalt_shapbg_masks(Zt.data_ptr(), nb, Fz, Z.stride(0), *paths, float(b.base_margin),
+                                         zmask.data_ptr(), zmargin.data_ptr(), stream)
+            _native.check(rc, "cobalt_shapbg_masks")
+            rc = lib.cobalt_treeshap_interventional(Xr.data_ptr(), n, F, X.stride(0), *paths, zmask.data_ptr(),
+                                                    zmargin.data_ptr(), nb, _native.ptr(xmargin), int(t0 == 0),
+                                                    int(t0 + nb == B), B, phi[r0:r0 + n].data_ptr(), stream)
+            _native.check(rc, "cobalt_treeshap_interventional")
+
+
+def shap_values_interventional(b: Booster, X, Z, *, model_output: str = "raw", n_trees: int | None = None,
+                               device=None):
+    """Interventional TreeSHAP values [N, F] float64 of ``X`` against the background rows ``Z``: a tensor in
+    gives a tensor on the device out, NumPy in gives NumPy out. A CUDA device runs ``csrc/shapbg.hip``, the
+    CPU runs :func:`~..models.booster.treeshap_interventional_host` (the definition). ``n_trees``: the first
+    trees only. ``ValueError`` for an empty background and for ``X`` or ``Z`` narrower than the model."""
+    prob = check_model_output(model_output)
+    b = _sliced(b, n_trees)
+    d = _device_of(X, device)
+    if d.type == "cuda":
+        Xt, Zt = _as_f32(X, d), _as_f32(Z, d)
+        _check_kernel_rows(b, Xt)
+        _check_kernel_rows(b, Zt)
+        phi = torch.empty((Xt.shape[0], Xt.shape[1]), dtype=torch.float64, device=d)
+        treeshap_interventional_gpu(b, Xt, Zt, phi, probability=prob)
+        return phi if isinstance(X, torch.Tensor) else phi.cpu().numpy()
+    Xn = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
+    Zn = Z.cpu().numpy() if isinstance(Z, torch.Tensor) else np.asarray(Z, dtype=np.float32)
+    check_background(b, Xn, Zn)
+    return treeshap_interventional_host(b, Xn, Zn, model_output)
