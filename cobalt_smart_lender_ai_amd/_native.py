@@ -73,6 +73,17 @@ _SIGS: dict[str, tuple] = {
                                   c_void_p, c_void_p]),
     "cobalt_bin_matrix_ld": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int,
                                      c_void_p, c_int64, c_void_p]),
+    # refresh.hip: leaf_index (X, n, F, ldx, nodes, tree_ptr, tile_ptr, n_tiles, tile_cap, n_trees, t0, t1, idx,
+    # stream); refresh (X, n, F, ldx, y, w, nodes, tree_ptr, tile_ptr, n_tiles, tile_cap, n_trees, tree_ptr_host,
+    # eta, lambda, alpha, mcw, gscale, hscale, seed, grad_bits, refresh_leaf, group_trees, idx, sums, stats,
+    # leaf_val, margin, stream)
+    "cobalt_leaf_index": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                  c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cobalt_refresh": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_int, c_int, c_int, c_void_p, c_double, c_double, c_double, c_double, c_double,
+                               c_double, ctypes.c_uint64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p]),
+    "cobalt_refresh_max_nodes": (c_int, []),
     # comm.cpp
     "cobalt_comm_load": (c_int, [c_char_p]),
     "cobalt_comm_last_error": (c_char_p, []),

@@ -231,6 +231,36 @@ class Booster:
 
         return predict_ops.staged_margins(self, X, device=device)
 
+    def predict_leaf(self, X, device: str | None = None, n_trees: int | None = None):
+        """The leaf every row lands in, per tree (XGBoost's ``pred_leaf=True``): int32 [N, T] node ids in this
+        booster's own numbering (indices into ``Tree.left_children``). NumPy in gives NumPy out; a tensor in
+        gives a tensor on its device out. ``n_trees``: the first trees only."""
+        from ..ops import predict_ops
+
+        return predict_ops.predict_leaf(self, X, device=device, n_trees=n_trees)
+
+    def refresh(self, X, y, sample_weight=None, *, refresh_leaf: bool = True, device: str | None = None,
+                return_margin: bool = False, leaf_index_bytes: int | None = None, dist=None, **overrides):
+        """XGBoost's ``process_type="update", updater="refresh"``: a NEW booster with this model's structure
+        (features, thresholds, default directions) whose node statistics (``sum_hessian``, ``base_weights``,
+        ``loss_changes``) are recomputed on the labelled rows ``(X, y)`` and, with ``refresh_leaf``, whose leaf
+        values are re-estimated too (:func:`refresh_host` is the definition). With ``refresh_leaf=False`` the
+        predictions are unchanged and the covers that path-dependent TreeSHAP, :meth:`expected_value` and
+        ``get_score("cover")`` read describe the rows given here. This booster is not modified.
+
+        ``overrides``: ``learning_rate``, ``reg_lambda``, ``reg_alpha``, ``min_child_weight``,
+        ``scale_pos_weight``, ``random_state``, ``grad_bits`` (default: this booster's ``train_params``, then
+        XGBoost's defaults; 17 bits). ``return_margin``: return ``(booster, margins of the new model on X)``.
+        ``leaf_index_bytes`` (GPU): see :func:`~..ops.predict_ops.refresh`; the result does not depend on it.
+        ``ValueError``: monotone-constrained boosters, data-parallel runs (``dist.world > 1``), empty ``X``,
+        labels outside {0, 1}, negative weights or weights that sum to 0. A subtree no row reaches gets cover
+        0 throughout; path-dependent TreeSHAP is not defined below such a node."""
+        from ..ops import predict_ops
+
+        new, margin = predict_ops.refresh(self, X, y, sample_weight, refresh_leaf=refresh_leaf, device=device,
+                                          leaf_index_bytes=leaf_index_bytes, dist=dist, **overrides)
+        return (new, margin) if return_margin else new
+
     @property
     def best_iteration(self) -> int | None:
         """Global index of the best round of an early-stopped fit (XGBoost's ``best_iteration``
@@ -801,6 +831,212 @@ def eval_curve_host(b: Booster, X: np.ndarray, y, sample_weight=None, metrics: S
 def sigmoid32(m: np.ndarray) -> np.ndarray:
     m = np.asarray(m, dtype=np.float32)
     return (np.float32(1.0) / (np.float32(1.0) + np.exp(-m))).astype(np.float32)
+
+
+# ------------------------------------------------------------------- leaf indices and leaf refresh
+def _leaf_of_tree(t: Tree, X: np.ndarray) -> np.ndarray:
+    """The node id (index into ``t.left_children``) of the leaf every row of ``X`` reaches, int32 [N]."""
+    N = X.shape[0]
+    nid = np.zeros(N, dtype=np.int32)
+    rows = np.arange(N)
+    while N:
+        lc = t.left_children[nid]
+        active = lc != -1
+        if not active.any():
+            break
+        v = X[rows, np.where(active, t.split_indices[nid], 0)]
+        go_left = np.where(np.isnan(v), t.default_left[nid] == 1, v < t.split_conditions[nid])
+        nid = np.where(active, np.where(go_left, lc, t.right_children[nid]), nid).astype(np.int32)
+    return nid
+
+
+def predict_leaf_host(b: Booster, X: np.ndarray, n_trees: int | None = None) -> np.ndarray:
+    """NumPy form of :meth:`Booster.predict_leaf` (CPU path and oracle of ``csrc/refresh.hip`` k_leaf_index):
+    int32 [N, T], the node id in the booster's own numbering of the leaf a row reaches in every tree, walked as
+    :func:`predict_margin_host` walks (``x < cond`` goes left, NaN takes ``default_left``)."""
+    X = np.asarray(X, dtype=np.float32)
+    if X.ndim != 2 or X.shape[1] < b.num_feature:
+        raise ValueError(f"X has shape {X.shape}, model needs [rows, >= {b.num_feature}]")
+    trees = b.trees[: (n_trees if n_trees is not None else b.num_trees)]
+    out = np.empty((X.shape[0], len(trees)), dtype=np.int32)
+    for i, t in enumerate(trees):
+        out[:, i] = _leaf_of_tree(t, X)
+    return out
+
+
+REFRESH_DEFAULTS = {"eta": 0.3, "reg_lambda": 1.0, "reg_alpha": 0.0, "min_child_weight": 1.0,
+                    "scale_pos_weight": 1.0, "seed": 0}
+_REFRESH_ALIAS = {"learning_rate": "eta", "lambda": "reg_lambda", "alpha": "reg_alpha", "random_state": "seed"}
+
+
+def refresh_params(b: Booster, overrides: dict[str, Any]) -> dict[str, Any]:
+    """The hyper-parameters of a refresh under their ``train_params`` names (``eta``, ``reg_lambda``,
+    ``reg_alpha``, ``min_child_weight``, ``scale_pos_weight``, ``seed``) plus ``grad_bits``: the overrides
+    (``learning_rate`` / ``random_state`` and XGBoost's ``lambda`` / ``alpha`` accepted), else the booster's
+    ``train_params``, else XGBoost's defaults; ``grad_bits`` defaults to the trainer's 17."""
+    from .gbdt_host import GRAD_BITS, QBITS
+
+    given = {}
+    for k, v in overrides.items():
+        k = _REFRESH_ALIAS.get(k, k)
+        if k not in REFRESH_DEFAULTS and k != "grad_bits":
+            raise TypeError(f"refresh() got an unexpected keyword argument {k!r}")
+        if v is not None:
+            given[k] = v
+    p: dict[str, Any] = {}
+    for k, dflt in REFRESH_DEFAULTS.items():
+        v = given.get(k, b.train_params.get(k))
+        p[k] = int(v if v is not None else dflt) if k == "seed" else float(v if v is not None else dflt)
+    p["grad_bits"] = int(given.get("grad_bits", QBITS))
+    if p["grad_bits"] not in GRAD_BITS:
+        raise ValueError(f"grad_bits must be one of {GRAD_BITS}")
+    p["overridden"] = sorted(k for k in given if k != "grad_bits")
+    return p
+
+
+def check_refresh_inputs(b: Booster, X_shape: tuple, y: np.ndarray, w: np.ndarray | None, dist=None) -> None:
+    """Everything a refresh refuses (``ValueError``), for the CPU and the GPU path alike, before anything is
+    computed or launched: boosters fitted under monotone constraints (a refresh would ignore the weight
+    bounds), data-parallel runs, an objective other than binary:logistic, an ``X`` that is empty or narrower
+    than the model, row-count mismatches, labels outside {0, 1}, negative (or NaN) weights and weights that sum
+    to 0."""
+    if b.monotone_constraints and any(b.monotone_constraints):
+        raise ValueError("refresh is not supported for boosters fitted under monotone_constraints: the "
+                         "recomputed weights would ignore the constraints' bounds")
+    if dist is not None and getattr(dist, "world", 1) > 1:
+        raise ValueError("refresh is not supported in data-parallel runs (dist.world > 1)")
+    if b.objective != "binary:logistic":
+        raise ValueError(f"refresh supports binary:logistic boosters, got {b.objective!r}")
+    if len(X_shape) != 2 or X_shape[1] < b.num_feature:
+        raise ValueError(f"X has shape {tuple(X_shape)}, model needs [rows, >= {b.num_feature}]")
+    n = int(X_shape[0])
+    if n == 0:
+        raise ValueError("refresh needs at least one row")
+    if y.ndim != 1 or y.shape[0] != n:
+        raise ValueError(f"X has {n} rows, y has shape {y.shape}")
+    if not bool(((y == 0) | (y == 1)).all()):
+        raise ValueError("refresh labels must be 0 or 1")
+    if w is not None:
+        if w.ndim != 1 or w.shape[0] != n:
+            raise ValueError(f"X has {n} rows, sample_weight has shape {w.shape}")
+        if not bool((w >= 0).all()):  # (NaN fails too)
+            raise ValueError("refresh sample weights must be non-negative")
+        if not float(np.sum(w, dtype=np.float64)) > 0:
+            raise ValueError("the refresh sample weights sum to zero")
+
+
+def refresh_row_weights(y32: np.ndarray, w32: np.ndarray | None, scale_pos_weight: float) -> np.ndarray:
+    """Row weights as the trainer forms them: float32 ``sample_weight`` x (float32 ``scale_pos_weight`` for
+    y = 1, else 1), the product in float32."""
+    pw = np.where(y32 == np.float32(1.0), np.float32(scale_pos_weight), np.float32(1.0)).astype(np.float32)
+    return pw if w32 is None else (w32.astype(np.float32) * pw).astype(np.float32)
+
+
+def refresh_node_stats(sums: np.ndarray, p: dict[str, Any], gscale: float,
+                       hscale: float) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """``(base_weight float32, sum_hessian float32, gain float64, leaf value float32)`` [n] of one tree from
+    its int64 node sums ``sums`` [n, 2] (the definition ``csrc/refresh.hip`` k_refresh_finalize follows): with
+    ``G = sum gq * (1 / gscale)`` and ``H = sum hq * (1 / hscale)`` in float64 (the trainer's form of the
+    division), ``base_weight = _calc_weight(G, H)``, ``sum_hessian = H``, ``gain = _calc_gain(G, H)`` (an
+    internal node's ``loss_change`` is ``(gain(left) + gain(right)) - gain(node)``) and the leaf value
+    ``float32(base_weight64 * eta)`` -- the trainer's expression for a new leaf."""
+    from .gbdt_host import _calc_gain, _thresh_l1
+
+    lam, alpha, mcw = p["reg_lambda"], p["reg_alpha"], p["min_child_weight"]
+    G = sums[:, 0].astype(np.float64) * (1.0 / gscale)
+    H = sums[:, 1].astype(np.float64) * (1.0 / hscale)
+    t = G if alpha == 0.0 else _thresh_l1(G, alpha)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        wgt = np.where((H < mcw) | (H <= 0.0), 0.0, -t / (H + lam))
+        gain = _calc_gain(G, H, lam, alpha, mcw)
+    return wgt.astype(np.float32), H.astype(np.float32), gain, (wgt * p["eta"]).astype(np.float32)
+
+
+def _refreshed_booster(b: Booster, trees: list[Tree], p: dict[str, Any]) -> Booster:
+    """A new booster around the refreshed trees: names, base score and ``train_params`` kept (the overridden
+    hyper-parameters updated), no ``source_config`` (the forest changed)."""
+    tp = dict(b.train_params)
+    for k in p["overridden"]:
+        tp[k] = p[k]
+    return Booster(trees=trees, feature_names=list(b.feature_names) if b.feature_names else b.feature_names,
+                   feature_types=list(b.feature_types) if b.feature_types else b.feature_types,
+                   base_score=b.base_score, num_feature=b.num_feature, objective=b.objective, train_params=tp,
+                   attributes=dict(b.attributes), source_config=None)
+
+
+def refreshed_tree(t: Tree, bw: np.ndarray, sh: np.ndarray, loss: np.ndarray, leaf: np.ndarray,
+                   refresh_leaf: bool) -> Tree:
+    """``t`` with its statistics replaced (float32 [n] each, in the tree's numbering) and, with
+    ``refresh_leaf``, its leaf values; the structure arrays are copies."""
+    cond = t.split_conditions.astype(np.float32).copy()
+    if refresh_leaf:
+        cond[t.is_leaf] = leaf[t.is_leaf]
+    return Tree(left_children=t.left_children.copy(), right_children=t.right_children.copy(),
+                parents=t.parents.copy(), split_indices=t.split_indices.copy(), split_conditions=cond,
+                default_left=t.default_left.copy(), base_weights=np.asarray(bw, np.float32).copy(),
+                loss_changes=np.asarray(loss, np.float32).copy(), sum_hessian=np.asarray(sh, np.float32).copy())
+
+
+def refresh_host(b: Booster, X: np.ndarray, y, sample_weight=None, *, refresh_leaf: bool = True, dist=None,
+                 node_sums: list | None = None, **overrides) -> tuple[Booster, np.ndarray]:
+    """NumPy form of :meth:`Booster.refresh` (CPU path and oracle of ``csrc/refresh.hip``): XGBoost's
+    ``process_type="update", updater="refresh"``. The structure of every tree is kept; tree by tree, in tree
+    order, with the float32 margin starting at the base margin:
+
+    1. the rows' gradient pairs are computed and quantised exactly as the trainer does for tree ``t``
+       (:func:`~.gbdt_host.gradients_host` with ``subsample = 1``, row key = row index, row weight =
+       :func:`refresh_row_weights`, scales = ``quant_scales(max weight, grad_bits)``);
+    2. every node on a row's root-to-leaf path receives the row's integers (int64 sums);
+    3. :func:`refresh_node_stats` gives ``base_weights``, ``sum_hessian`` and ``loss_changes`` (a node no row
+       reaches: weight 0, cover 0) and, with ``refresh_leaf``, the leaf values;
+    4. the margin takes the row's (new) leaf value of tree ``t``, a float32 add -- the running sum of
+       ``predict_margin(n_trees=t + 1)`` of the model being produced.
+
+    Returns ``(new booster, its margins on X)``; ``b`` is not modified. ``overrides``: see
+    :func:`refresh_params`. ``node_sums``: a list that receives every tree's int64 [n, 2] node sums.
+    ``ValueError``: see :func:`check_refresh_inputs`. Note: ``base_weights`` is the weight itself, as
+    XGBoost's refresh updater stores it; the trainer stores the weight times ``eta``."""
+    from .gbdt_host import HostGbdtParams, gradients_host, quant_scales
+
+    X = np.asarray(X, dtype=np.float32)
+    y32 = np.asarray(y, dtype=np.float32).reshape(-1)
+    w32 = None if sample_weight is None else np.asarray(sample_weight, dtype=np.float32).reshape(-1)
+    check_refresh_inputs(b, X.shape, y32, w32, dist)
+    p = refresh_params(b, overrides)
+    wt = refresh_row_weights(y32, w32, p["scale_pos_weight"])
+    gscale, hscale = quant_scales(float(wt.max()), p["grad_bits"])
+    hp = HostGbdtParams(max_depth=0, eta=p["eta"], reg_lambda=p["reg_lambda"], reg_alpha=p["reg_alpha"], gamma=0.0,
+                        min_child_weight=p["min_child_weight"], subsample=1.0, seed=p["seed"], gscale=gscale,
+                        hscale=hscale, quant=True, qbits=p["grad_bits"])
+    N = X.shape[0]
+    margin = np.full(N, np.float32(b.base_margin), dtype=np.float32)
+    trees = []
+    for ti, t in enumerate(b.trees):
+        leaf = _leaf_of_tree(t, X)
+        gq, hq = gradients_host(margin, y32, wt, hp, ti)
+        sums = np.zeros((t.num_nodes, 2), dtype=np.int64)
+        np.add.at(sums[:, 0], leaf, gq)
+        np.add.at(sums[:, 1], leaf, hq)
+        # internal nodes = the sum of their two children, children first (any numbering: post-order)
+        order, stack = [], [0]
+        while stack:
+            j = stack.pop()
+            order.append(j)
+            if t.left_children[j] != -1:
+                stack += [int(t.left_children[j]), int(t.right_children[j])]
+        for j in reversed(order):
+            if t.left_children[j] != -1:
+                sums[j] = sums[t.left_children[j]] + sums[t.right_children[j]]
+        if node_sums is not None:
+            node_sums.append(sums)
+        bw, sh, gain, lv = refresh_node_stats(sums, p, gscale, hscale)
+        split = ~t.is_leaf
+        loss = np.zeros(t.num_nodes, dtype=np.float32)
+        loss[split] = ((gain[t.left_children[split]] + gain[t.right_children[split]]) - gain[split]).astype(np.float32)
+        nt = refreshed_tree(t, bw, sh, loss, lv, refresh_leaf)
+        trees.append(nt)
+        margin = (margin + nt.split_conditions[leaf]).astype(np.float32)
+    return _refreshed_booster(b, trees, p), margin
 
 
 # ------------------------------------------------------------------------- partial dependence

@@ -1369,6 +1369,40 @@ class GBDTClassifier:
         pred = (p > 0.5).astype(np.int64)
         return self.classes_[pred] if getattr(self, "classes_", None) is not None and len(self.classes_) == 2 else pred
 
+    def apply(self, X, iteration_range=None) -> np.ndarray:
+        """The leaf every row lands in, per tree (``XGBClassifier.apply``): int32 [N, trees] node ids in the
+        booster's numbering, over the trees :meth:`predict_proba` would score (``iteration_range``, else up to
+        ``best_iteration``)."""
+        n = self._n_trees(iteration_range)
+        leaf = self.get_booster().predict_leaf(self._matrix(X), device=self.device, n_trees=n)
+        return leaf.cpu().numpy() if isinstance(leaf, torch.Tensor) else np.asarray(leaf)
+
+    def refresh(self, X, y, sample_weight=None, refresh_leaf: bool = True) -> "GBDTClassifier":
+        """A NEW estimator whose trees keep this model's structure and whose node statistics (and, with
+        ``refresh_leaf``, leaf values) are re-estimated on ``(X, y)`` with this estimator's hyper-parameters:
+        XGBoost's ``process_type="update", updater="refresh"`` (:meth:`Booster.refresh`). This estimator is
+        not modified; the result saves and loads like a fitted one."""
+        b = self.get_booster()
+        y_np = np.asarray(y.to_numpy() if hasattr(y, "to_numpy") else y).reshape(-1)
+        classes = getattr(self, "classes_", None)
+        if classes is not None and len(classes) == 2:
+            if not np.isin(y_np, classes).all():
+                raise ValueError("refresh labels must be among the training classes")
+            yb = (y_np == classes[-1]).astype(np.float32)
+        else:
+            yb = y_np.astype(np.float32)
+        p = self._train_params()
+        new = type(self)(**self.get_params())
+        new._Booster = b.refresh(self._matrix(X), yb, sample_weight, refresh_leaf=refresh_leaf, device=self.device,
+                                 learning_rate=float(p.learning_rate), reg_lambda=float(p.reg_lambda),
+                                 reg_alpha=float(p.reg_alpha), min_child_weight=float(p.min_child_weight),
+                                 scale_pos_weight=float(p.scale_pos_weight), random_state=int(p.random_state),
+                                 grad_bits=int(p.grad_bits))
+        for k in ("classes_", "n_classes_", "n_features_in_", "feature_names_in_"):
+            if hasattr(self, k):
+                setattr(new, k, getattr(self, k))
+        return new
+
     def score(self, X, y) -> float:
         from ..metrics.classification import accuracy_score
 

@@ -2,7 +2,8 @@
 :class:`Booster`.
 
 GPU path: gfx950 kernels in ``csrc/predict.hip`` (forest packed once per booster and device, cached),
-``csrc/shapint.hip``, ``csrc/shapbg.hip``, ``csrc/evalcurve.hip``, ``csrc/pdp.hip`` and ``csrc/permimp.hip``.
+``csrc/shapint.hip``, ``csrc/shapbg.hip``, ``csrc/evalcurve.hip``, ``csrc/pdp.hip``, ``csrc/permimp.hip`` and
+``csrc/refresh.hip`` (leaf indices, leaf refresh).
 CPU path: the NumPy reference implementations in ``models/booster.py``.
 """
 from __future__ import annotations
@@ -15,10 +16,13 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..models.booster import (Booster, Tree, check_background, check_eval_inputs, check_model_output,
-                              check_perm_inputs, eval_curve_host, partial_dependence_host, permutation_scores_host,
-                              predict_margin_host, sigmoid32, staged_margins_host, treeshap_host,
+from ..models.booster import (Booster, Tree, _refreshed_booster, check_background, check_eval_inputs,
+                              check_model_output, check_perm_inputs, check_refresh_inputs, eval_curve_host,
+                              partial_dependence_host, permutation_scores_host, predict_leaf_host,
+                              predict_margin_host, refresh_host, refresh_params, refresh_row_weights,
+                              refreshed_tree, sigmoid32, staged_margins_host, treeshap_host,
                               treeshap_interactions_host, treeshap_interventional_host)
+from ..models.gbdt_host import quant_scales
 from ..config import knob
 
 # LDS tile capacity in nodes: a model's tile is max(this, its largest tree), at most MAX_TILE_NODES
@@ -258,6 +262,8 @@ class _GpuForest:
     max_len: int = 0
     tab_ptr: torch.Tensor | None = None   # Fast-TreeSHAP pattern tables (None: direct kernel)
     table: torch.Tensor | None = None
+    unpack: torch.Tensor | None = None    # packed node -> booster node id (None once known: the identity)
+    unpack_known: bool = False
 
 
 def gpu_forest(b: Booster, device: torch.device, n_trees: int | None = None, with_shap: bool = False) -> _GpuForest:
@@ -713,6 +719,160 @@ def permutation_scores(b: Booster, X, y, feats, perm, *, n_trees: int | None = N
                     auc[i0 + i, r0 + r] = roc_auc(ypos, m[1 + i * (r1 - r0) + r])
         scores["auc"] = auc
     return {m: base[m] for m in metrics}, {m: scores[m] for m in metrics}
+
+
+# ------------------------------------------------------------------- leaf indices and leaf refresh
+# Bytes of the tree-major uint16 [trees, N] leaf-index buffer of csrc/refresh.hip (2 N bytes per tree): the
+# forest is processed in groups of trees whose buffer fits. 1 GiB holds the 300-tree model's indices of 1.7M
+# rows in one group and still takes 53 trees at a time at 10M rows (a group costs one extra launch and a
+# re-staging of the rows); results do not depend on it.
+LEAF_INDEX_BYTES = 1 << 30
+REFRESH_MAX_NODES = 6301       # largest tree of the refresh kernels (csrc/refresh.hip cobalt_refresh_max_nodes)
+
+
+def _unpack_table(b: Booster, gf: _GpuForest) -> torch.Tensor | None:
+    """int32 [M] on the forest's device: booster node id of every packed node (the inverse of pack_forest's
+    BFS renumbering), or None when the booster's numbering already is the packed one (the trainer's is)."""
+    if gf.unpack_known:
+        return gf.unpack
+    orders = [np.asarray(_bfs_order(t), dtype=np.int32) for t in b.trees[:gf.n_trees]]
+    if any((o != np.arange(len(o), dtype=np.int32)).any() for o in orders):
+        gf.unpack = torch.from_numpy(np.concatenate(orders)).to(gf.nodes.device)
+    gf.unpack_known = True
+    return gf.unpack
+
+
+def _group_trees(n_rows: int, n_trees: int, leaf_index_bytes: int | None) -> int:
+    nbytes = LEAF_INDEX_BYTES if leaf_index_bytes is None else int(leaf_index_bytes)
+    if nbytes < 1:
+        raise ValueError(f"leaf_index_bytes must be positive, got {leaf_index_bytes}")
+    return max(1, min(n_trees, nbytes // max(2 * n_rows, 1)))
+
+
+def predict_leaf_gpu(b: Booster, X: torch.Tensor, n_trees: int | None = None,
+                     leaf_index_bytes: int | None = None) -> torch.Tensor:
+    """int32 [N, T] on the device of ``X``: the booster node id of every row's leaf in every tree
+    (``csrc/refresh.hip`` k_leaf_index on the current stream, then a gather through the per-tree table that
+    undoes the packer's renumbering). ``X`` as for :func:`predict_gpu`. The device buffer of packed indices
+    is tree-major uint16 and bounded by ``leaf_index_bytes`` (default ``LEAF_INDEX_BYTES``): the trees are
+    taken in groups."""
+    _check_kernel_rows(b, X)
+    gf = gpu_forest(b, X.device, n_trees)
+    N, F = X.shape
+    T = gf.n_trees
+    out = torch.empty((N, T), dtype=torch.int32, device=X.device)
+    if N == 0 or T == 0:
+        return out
+    lib = _native.lib()
+    table = _unpack_table(b, gf)
+    per = _group_trees(N, T, leaf_index_bytes)
+    idx = torch.empty((per, N), dtype=torch.int16, device=X.device)  # (uint16 bits)
+    for t0 in range(0, T, per):
+        t1 = min(T, t0 + per)
+        rc = lib.cobalt_leaf_index(X.data_ptr(), N, F, X.stride(0), gf.nodes.data_ptr(), gf.tree_ptr.data_ptr(),
+                                   gf.tile_ptr.data_ptr(), gf.n_tiles, gf.tile_cap, T, t0, t1, idx.data_ptr(),
+                                   _native.stream_handle())
+        _native.check(rc, "cobalt_leaf_index")
+        packed = idx[: t1 - t0].to(torch.int32) & 0xFFFF
+        if table is not None:
+            packed = table[(packed + gf.tree_ptr[t0:t1, None]).long()]
+        out[:, t0:t1] = packed.t()
+    return out
+
+
+def predict_leaf(b: Booster, X, device=None, n_trees: int | None = None):
+    d = _device_of(X, device)
+    if n_trees is not None and not 0 <= n_trees <= b.num_trees:
+        raise ValueError(f"n_trees must be in [0, {b.num_trees}], got {n_trees}")
+    if d.type == "cuda":
+        out = predict_leaf_gpu(b, _as_f32(X, d), n_trees)
+        return out if isinstance(X, torch.Tensor) else out.cpu().numpy()
+    Xn = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
+    out = predict_leaf_host(b, Xn, n_trees)
+    return torch.from_numpy(out) if isinstance(X, torch.Tensor) else out
+
+
+def refresh_gpu(b: Booster, X: torch.Tensor, y: torch.Tensor, w: torch.Tensor, p: dict, gscale: float,
+                hscale: float, refresh_leaf: bool, leaf_index_bytes: int | None = None):
+    """Launch ``csrc/refresh.hip`` over all trees of ``b`` on the current stream (2 T + a few launches, no host
+    synchronisation in between). ``X`` as for :func:`predict_gpu`; ``y`` / ``w``: contiguous float32 [N] on its
+    device (``w`` = the row weights of :func:`~..models.booster.refresh_row_weights`); ``p``:
+    :func:`~..models.booster.refresh_params`. Returns device tensors in PACKED node order (``pack_forest``):
+    ``(sums int64 [M, 2], stats float32 [3, M] = base weight / cover / loss change, leaf values float32 [M],
+    margins float32 [N])``. ``RuntimeError`` for a tree outside the kernels' LDS tables, before any launch."""
+    _check_kernel_rows(b, X)
+    N, F = X.shape
+    for name, v in (("y", y), ("w", w)):
+        if v.dtype != torch.float32 or v.dim() != 1 or v.shape[0] != N or v.device != X.device or not v.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 [{N}] tensor on {X.device}")
+    gf = gpu_forest(b, X.device)
+    T = gf.n_trees
+    tptr = np.ascontiguousarray(pack_forest(b, None, gf.tile_cap)[1], dtype=np.int32)
+    M = int(tptr[-1])
+    biggest = int(np.diff(tptr).max()) if T else 0
+    if biggest > REFRESH_MAX_NODES:
+        raise RuntimeError(f"a tree with {biggest} nodes exceeds the refresh kernels' LDS tables "
+                           f"({REFRESH_MAX_NODES} nodes)")
+    per = _group_trees(N, T, leaf_index_bytes)
+    idx = torch.empty((per, N), dtype=torch.int16, device=X.device)
+    sums = torch.empty((M, 2), dtype=torch.int64, device=X.device)
+    stats = torch.empty((3, M), dtype=torch.float32, device=X.device)
+    leaf_val = torch.empty(M, dtype=torch.float32, device=X.device)
+    margin = torch.full((N,), b.base_margin, dtype=torch.float32, device=X.device)
+    rc = _native.lib().cobalt_refresh(X.data_ptr(), N, F, X.stride(0), y.data_ptr(), w.data_ptr(), gf.nodes.data_ptr(),
+                                      gf.tree_ptr.data_ptr(), gf.tile_ptr.data_ptr(), gf.n_tiles, gf.tile_cap, T,
+                                      tptr.ctypes.data, p["eta"], p["reg_lambda"], p["reg_alpha"],
+                                      p["min_child_weight"], gscale, hscale, int(p["seed"]) & ((1 << 64) - 1),
+                                      p["grad_bits"], int(bool(refresh_leaf)), per, idx.data_ptr(), sums.data_ptr(),
+                                      stats.data_ptr(), leaf_val.data_ptr(), margin.data_ptr(),
+                                      _native.stream_handle())
+    _native.check(rc, "cobalt_refresh")
+    return sums, stats, leaf_val, margin
+
+
+def refresh(b: Booster, X, y, sample_weight=None, *, refresh_leaf: bool = True, device=None,
+            leaf_index_bytes: int | None = None, dist=None, node_sums: list | None = None, **overrides):
+    """``(new booster, its margins on X)``: :meth:`Booster.refresh`. A CUDA device runs ``csrc/refresh.hip``
+    (byte-identical to the CPU path, :func:`~..models.booster.refresh_host`, the definition). The margins are a
+    tensor on the device for a tensor ``X``, else NumPy. ``leaf_index_bytes``: bound of the device buffer of
+    leaf indices (default ``LEAF_INDEX_BYTES``; the trees are processed in groups that fit, and the result
+    does not depend on the grouping). ``node_sums``: a list that receives every tree's int64 [n, 2] node sums
+    in the booster's numbering. ``ValueError`` (:func:`~..models.booster.check_refresh_inputs`) before any
+    launch."""
+    d = _device_of(X, device)
+    y32 = _host_vec(y)
+    w32 = None if sample_weight is None else _host_vec(sample_weight)
+    if d.type != "cuda":
+        Xn = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
+        new, margin = refresh_host(b, Xn, y32, w32, refresh_leaf=refresh_leaf, dist=dist, node_sums=node_sums,
+                                   **overrides)
+        return new, (torch.from_numpy(margin) if isinstance(X, torch.Tensor) else margin)
+    # labels and weights are a few bytes per row: they are checked, and the row weights formed, on the host
+    check_refresh_inputs(b, tuple(X.shape), y32, w32, dist)
+    p = refresh_params(b, overrides)
+    wt = refresh_row_weights(y32, w32, p["scale_pos_weight"])
+    gscale, hscale = quant_scales(float(wt.max()), p["grad_bits"])
+    Xt = _as_f32(X, d)
+    sums, stats, leaf_val, margin = refresh_gpu(b, Xt, torch.as_tensor(y32, device=d), torch.as_tensor(wt, device=d),
+                                                p, gscale, hscale, refresh_leaf, leaf_index_bytes)
+    sums_h, stats_h, leaf_h = sums.cpu().numpy(), stats.cpu().numpy(), leaf_val.cpu().numpy()
+    trees, n0 = [], 0
+    for t in b.trees:
+        order = np.asarray(_bfs_order(t), dtype=np.int64)  # packed index -> booster node id
+        n1 = n0 + len(order)
+        cols = []
+        for src in (stats_h[0, n0:n1], stats_h[1, n0:n1], stats_h[2, n0:n1], leaf_h[n0:n1]):
+            a = np.empty(len(order), dtype=np.float32)
+            a[order] = src
+            cols.append(a)
+        if node_sums is not None:
+            s = np.empty((len(order), 2), dtype=np.int64)
+            s[order] = sums_h[n0:n1]
+            node_sums.append(s)
+        trees.append(refreshed_tree(t, *cols, refresh_leaf))
+        n0 = n1
+    new = _refreshed_booster(b, trees, p)
+    return new, (margin if isinstance(X, torch.Tensor) else margin.cpu().numpy())
 
 
 def shap_values(b: Booster, X, device=None):
