@@ -41,6 +41,11 @@ constexpr int kCsvLdsWords = kCsvWords + kCsvWords / 64;
 
 // field status codes (mirrored in prep/csv_gpu.py)
 constexpr uint8_t kStInt = 0, kStNull = 1, kStTrue = 2, kStFalse = 3, kStStr = 4, kStNeedHost = 5, kStFrac = 6;
+// kStBigInt: int64 syntax and range, but past 2^53 (the value is the rounded float64; an int64 column
+// cannot hold it). kStHostNum: text unless the host reader would make the column numeric
+// (host_only_number). The caller refuses the file in both cases (prep/csv_gpu.py).
+// kStNegZero: "-0", int64 syntax (value +0.0).
+constexpr uint8_t kStBigInt = 7, kStHostNum = 8, kStNegZero = 9;
 
 __device__ __forceinline__ int count_byte(uint32_t w, uint32_t c) {
   const uint32_t x = w ^ (c * 0x01010101u);
@@ -820,18 +825,45 @@ __constant__ double kPow10dd[581][2] = {
     {0x1.06b0bb1fb384cp+960, -0x1.241be701561d0p+906},
     {0x1.485ce9e7a065fp+963, -0x1.6d22e0c1aba44p+909}};
 
+// 10^k * 2^128 for k = -308..-291, same format: a <= 19-digit mantissa puts the power of ten of a
+// 17-digit decimal down to 10^-290 this far below the table above, and 10^k itself is no normal
+// double-double there
+constexpr int kDdLow = 18, kDdLowShift = 128;
+__constant__ double kPow10ddLow[kDdLow][2] = {
+    {0x1.cc359e067a349p-896, -0x1.1048236dbc6b4p-950},
+    {0x1.1fa182c40c60dp-892, 0x1.d5d2e9db6a3d0p-946},
+    {0x1.6789e3750f791p-889, -0x1.6970b75b76679p-944},
+    {0x1.c16c5c5253575p-886, 0x1.e198d66d5ff4ap-944},
+    {0x1.18e3b9b374169p-882, 0x1.259ff0c08b7f2p-937},
+    {0x1.5f1ca820511c3p-879, 0x1.b783f678572f7p-933},
+    {0x1.b6e3d22865634p-876, 0x1.2564f4166cfb5p-930},
+    {0x1.124e63593f5e1p-872, -0x1.48a0e771fbe2fp-926},
+    {0x1.56e1fc2f8f359p-869, -0x1.3592429cf5b75p-924},
+    {0x1.ac9a7b3b7302fp-866, 0x1.f424b2ef336b5p-923},
+    {0x1.0be08d0527e1dp-862, 0x1.a712ddfab0046p-916},
+    {0x1.4ed8b04671da5p-859, -0x1.de50d50d47f51p-914},
+    {0x1.a28edc580e50ep-856, -0x1.5794294267c93p-913},
+    {0x1.059949b708f29p-852, -0x1.1ad79339301bbp-906},
+    {0x1.46ff9c24cb2f3p-849, -0x1.8635e01df08a9p-905},
+    {0x1.98bf832dfdfb0p-846, -0x1.79f0d6095b2b5p-900},
+    {0x1.feef63f97d79cp-843, -0x1.d86d0b8bb1f62p-897},
+    {0x1.3f559e7bee6c1p-839, 0x1.b177b191618c5p-894}};
+
 __constant__ double kPow10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
                                   1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
 
 // m * 10^dexp for a <= 19-digit mantissa outside Clinger's range: the product with a double-double
 // power of ten carries ~2^-104 relative error, so its leading double is the correctly rounded result
 // unless the exact value lies within that error of a rounding boundary (a tie, or a binade edge) --
-// then the caller defers to the host. Returns false for that case and for |dexp| > 290.
+// then the caller defers to the host. Returns false for that case and for dexp outside -308..290.
 __device__ __forceinline__ bool dd_convert(uint64_t m, int dexp, double& out) {
-  if (dexp < -kDdPow || dexp > kDdPow) return false;
+  if (dexp < -kDdPow - kDdLow || dexp > kDdPow) return false;
   const double mh = (double)m;
   const double ml = (double)(int64_t)(m - (uint64_t)mh);  // exact, |m - mh| <= 2^10
-  const double ph = kPow10dd[dexp + kDdPow][0], pl = kPow10dd[dexp + kDdPow][1];
+  // below 10^-290 the product is formed times 2^128 (exact) and scaled back once it is rounded
+  const bool low = dexp < -kDdPow;
+  const double* pw = low ? kPow10ddLow[dexp + kDdPow + kDdLow] : kPow10dd[dexp + kDdPow];
+  const double ph = pw[0], pl = pw[1];
   const double p = mh * ph;
   double e = fma(mh, ph, -p);
   e = fma(mh, pl, e);
@@ -840,13 +872,13 @@ __device__ __forceinline__ bool dd_convert(uint64_t m, int dexp, double& out) {
   const double lo = e - (hi - p);
   const uint64_t bits = (uint64_t)__double_as_longlong(hi) & 0x7FFFFFFFFFFFFFFFull;
   const int ex = (int)(bits >> 52);
-  if (ex == 0 || ex >= 0x7FF) return false;  // subnormal / overflow
+  if (ex <= (low ? kDdLowShift : 0) || ex >= 0x7FF) return false;  // subnormal / overflow
   const double half_ulp = ldexp(1.0, ex - 1076);
   const double err = fabs(hi) * 0x1p-98;
   // a power of two has half the spacing below it: the rounding boundary there is a quarter ulp away
   const bool edge = (bits & 0xFFFFFFFFFFFFFull) == 0;
   if (fabs(lo) >= ((edge && lo < 0.0) ? 0.5 * half_ulp : half_ulp) - err) return false;
-  out = hi;
+  out = low ? ldexp(hi, -kDdLowShift) : hi;  // exact: the result is a normal double
   return true;
 }
 
@@ -954,35 +986,37 @@ __device__ bool pandas_xstrtod(const uint8_t* __restrict__ buf, int64_t i, int64
   return true;
 }
 
-// Status + value of one field (see the status codes above). pandas_fp: float-syntax fields take
-// pandas' default conversion (pandas_xstrtod) instead of the correctly rounded one.
-__device__ uint8_t parse_field(const uint8_t* __restrict__ buf, const Field& f, double& out, bool pandas_fp = false) {
-  out = __builtin_nan("");
-  if (is_na(buf, f)) return kStNull;
-  const int64_t len = f.e - f.s;
-  if (len == 4 && (eq_lit(buf, f, "True", 4) || eq_lit(buf, f, "TRUE", 4) || eq_lit(buf, f, "true", 4))) return kStTrue;
-  if (len == 5 && (eq_lit(buf, f, "False", 5) || eq_lit(buf, f, "FALSE", 5) || eq_lit(buf, f, "false", 5)))
-    return kStFalse;
-  int64_t i = f.s;
+// Status + value of the number in [s, e), or kStStr. pandas_fp: float-syntax fields take pandas'
+// default conversion (pandas_xstrtod) instead of the correctly rounded one.
+__device__ __forceinline__ uint8_t parse_number(const uint8_t* __restrict__ buf, int64_t s, int64_t e, double& out,
+                                                bool pandas_fp) {
+  int64_t i = s;
   bool neg = false, plus = false;
   if (buf[i] == '+' || buf[i] == '-') { neg = buf[i] == '-'; plus = !neg; ++i; }
-  if (f.e - i == 3 && (eq_lit(buf, Field{i, f.e, false}, "inf", 3) || eq_lit(buf, Field{i, f.e, false}, "Inf", 3))) {
+  // "inf" / "infinity" in any letter case, as pyarrow's and pandas' float parsers read them
+  if ((e - i == 3 || e - i == 8) && (buf[i] | 0x20) == 'i') {
+    const char* lit = "infinity";
+    bool is_inf = true;
+    for (int64_t j = i; j < e; ++j) is_inf &= (buf[j] | 0x20) == (uint8_t)lit[j - i];
+    if (!is_inf) return kStStr;
     out = neg ? -__builtin_inf() : __builtin_inf();
     return kStFrac;
   }
   uint64_t m = 0;
   int nd = 0, dexp = 0;
   bool any = false, frac = plus, lost = false;  // pyarrow: "+5" is not int64 syntax, but is a float
-  for (; i < f.e; ++i) {
+  for (; i < e; ++i) {
     const unsigned dg = (unsigned)buf[i] - '0';
     if (dg > 9) break;
     any = true;
     if (nd < 19) { m = m * 10 + dg; if (m) ++nd; }
     else { ++dexp; lost |= dg != 0; }
   }
-  if (i < f.e && buf[i] == '.') {
+  const uint64_t mint = m;  // the integer part (its first 19 digits when dexp > 0)
+  const int dint = dexp;
+  if (i < e && buf[i] == '.') {
     frac = true;
-    for (++i; i < f.e; ++i) {
+    for (++i; i < e; ++i) {
       const unsigned dg = (unsigned)buf[i] - '0';
       if (dg > 9) break;
       any = true;
@@ -991,14 +1025,14 @@ __device__ uint8_t parse_field(const uint8_t* __restrict__ buf, const Field& f, 
     }
   }
   if (!any) return kStStr;
-  if (i < f.e && (buf[i] == 'e' || buf[i] == 'E')) {
+  if (i < e && (buf[i] == 'e' || buf[i] == 'E')) {
     frac = true;
     ++i;
     bool eneg = false;
-    if (i < f.e && (buf[i] == '+' || buf[i] == '-')) { eneg = buf[i] == '-'; ++i; }
+    if (i < e && (buf[i] == '+' || buf[i] == '-')) { eneg = buf[i] == '-'; ++i; }
     int ex = 0;
     bool ed = false;
-    for (; i < f.e; ++i) {
+    for (; i < e; ++i) {
       const unsigned dg = (unsigned)buf[i] - '0';
       if (dg > 9) break;
       ed = true;
@@ -1007,31 +1041,95 @@ __device__ uint8_t parse_field(const uint8_t* __restrict__ buf, const Field& f, 
     if (!ed) return kStStr;
     dexp += eneg ? -ex : ex;
   }
-  if (i != f.e) return kStStr;
+  if (i != e) return kStStr;
+  const int64_t b = s + ((neg || plus) ? 1 : 0);  // the field after its sign
   if (pandas_fp && frac) {  // syntax checked above: the digits and exponent are well formed
-    int64_t b = f.s;
-    if (buf[b] == '+' || buf[b] == '-') ++b;
+    // pandas tries int64, then uint64 first: integer digits below the int64 range can leave the column text
+    if (neg && (dint > 0 || mint > (1ull << 63))) return kStHostNum;
     double v;
-    if (!pandas_xstrtod(buf, b, f.e, neg, v)) return kStNeedHost;
+    if (!pandas_xstrtod(buf, b, e, neg, v)) return kStNeedHost;
     out = v;
     return kStFrac;
   }
   if (lost) return kStNeedHost;
   double v;
+  uint8_t st = frac ? kStFrac : kStInt;
   if (m == 0) {
     v = 0.0;
   } else if (!frac) {
     if (dexp != 0) return kStNeedHost;  // > 19 integer digits
     v = (double)m;                      // correctly rounded u64 -> f64
+    if (m > (1ull << 53)) {             // not exact in the frame's float64 (off the common path)
+      // past int64 the host readers read a float (pandas: uint64, left to it)
+      const bool i64 = m <= (1ull << 63) - (neg ? 0 : 1);
+      if (pandas_fp) {
+        if (!i64 || !pandas_xstrtod(buf, b, e, neg, v)) return kStNeedHost;
+        out = v;
+        return kStBigInt;
+      }
+      st = i64 ? kStBigInt : kStFrac;
+    }
   } else if (m <= (1ull << 53) && dexp >= -22 && dexp <= 22) {
     v = (double)m;
     v = dexp >= 0 ? v * kPow10[dexp] : v / kPow10[-dexp];
   } else if (!dd_convert(m, dexp, v)) {
     return kStNeedHost;
   }
-  // integer syntax "-0" is int64 0 (+0.0 after the float64 cast); "-0.0" keeps its sign
-  out = neg && (frac || m != 0) ? -v : v;
-  return frac ? kStFrac : kStInt;
+  // integer syntax "-0" is int64 0 (+0.0 after the float64 cast) but -0.0 in a float column: the caller
+  // sets the sign once it knows the column (kStNegZero); "-0.0" keeps its sign
+  out = neg && (st != kStInt || m != 0) ? -v : v;
+  return (st == kStInt && neg && m == 0) ? kStNegZero : st;
+}
+
+__device__ __forceinline__ bool is_blank(uint8_t c) { return c == ' ' || c == '\t'; }
+
+// Text that only pyarrow reads as a number: "0x1F" (int64), and "nan" in another letter case, signed or
+// with a "(...)" payload (float64 NaN). [s, e): the field without surrounding blanks.
+__device__ bool host_only_number(const uint8_t* __restrict__ buf, int64_t s, int64_t e) {
+  if (e - s >= 3 && buf[s] == '0' && (buf[s + 1] | 0x20) == 'x') {
+    for (int64_t i = s + 2; i < e; ++i) {
+      const uint8_t c = buf[i], l = c | 0x20;
+      if (!((unsigned)c - '0' <= 9u || (l >= 'a' && l <= 'f'))) return false;
+    }
+    return true;
+  }
+  if (s < e && (buf[s] == '+' || buf[s] == '-')) ++s;
+  if (e - s < 3 || (buf[s] | 0x20) != 'n' || (buf[s + 1] | 0x20) != 'a' || (buf[s + 2] | 0x20) != 'n') return false;
+  if (e - s == 3) return true;
+  if (buf[s + 3] != '(' || buf[e - 1] != ')') return false;
+  for (int64_t i = s + 4; i < e - 1; ++i) {
+    const uint8_t c = buf[i], l = c | 0x20;
+    if (!((unsigned)c - '0' <= 9u || (l >= 'a' && l <= 'z') || c == '_')) return false;
+  }
+  return true;
+}
+
+// Status + value of one field (see the status codes above). The readers this one stands in for strip
+// blanks (' ', '\t') around a number but not around a missing-value or bool literal, so a field that is
+// no number as it stands is tried once more without them.
+__device__ uint8_t parse_field(const uint8_t* __restrict__ buf, const Field& f, double& out, bool pandas_fp = false) {
+  out = __builtin_nan("");
+  if (is_na(buf, f)) return kStNull;
+  const int64_t len = f.e - f.s;
+  if (len == 4 && (eq_lit(buf, f, "True", 4) || eq_lit(buf, f, "TRUE", 4) || eq_lit(buf, f, "true", 4))) return kStTrue;
+  if (len == 5 && (eq_lit(buf, f, "False", 5) || eq_lit(buf, f, "FALSE", 5) || eq_lit(buf, f, "false", 5)))
+    return kStFalse;
+  int64_t s = f.s, e = f.e;
+  for (int pass = 0;; ++pass) {
+    const uint8_t st = parse_number(buf, s, e, out, pandas_fp);
+    if (st != kStStr) {
+      // pandas reads a padded "inf" as text
+      if (pass && pandas_fp && __builtin_isinf(out)) { out = __builtin_nan(""); return kStHostNum; }
+      return st;
+    }
+    if (pass) break;
+    while (s < e && is_blank(buf[s])) ++s;
+    while (e > s && is_blank(buf[e - 1])) --e;
+    if (s == e) return kStStr;
+    if (s == f.s && e == f.e) break;
+  }
+  out = __builtin_nan("");
+  return host_only_number(buf, s, e) ? kStHostNum : kStStr;
 }
 
 template <bool kPandasFp>
@@ -1063,7 +1161,8 @@ struct FieldReader {
 
 __global__ __launch_bounds__(256) void k_csv_hash(const uint8_t* __restrict__ buf, const int64_t* __restrict__ fend,
                                                   int64_t nrows, int C, const int32_t* __restrict__ cols, int ncols,
-                                                  unsigned long long* __restrict__ out) {
+                                                  unsigned long long* __restrict__ out,
+                                                  unsigned long long* __restrict__ badq) {
   const int j = blockIdx.y;
   const int c = cols[j];
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
@@ -1075,13 +1174,18 @@ __global__ __launch_bounds__(256) void k_csv_hash(const uint8_t* __restrict__ bu
       uint64_t w = 0;
       int nb = 0, len = 0;
       uint32_t ch;
-      while (rd.next(ch)) {
+      bool lone = false;  // a quote that is neither enclosing nor half of a "" pair: not RFC 4180
+      while (true) {
+        const int64_t p0 = rd.p;
+        if (!rd.next(ch)) break;
+        lone |= ch == '"' && rd.p - p0 == 1;
         w |= (uint64_t)ch << (8 * nb);
         ++len;
         if (++nb == 8) { h = splitmix64(h ^ w); w = 0; nb = 0; }
       }
       h = splitmix64(h ^ w ^ ((uint64_t)len << 56));
       if (h == 0) h = 1;
+      if (lone) atomicAdd(badq, 1ull);
     }
     out[(int64_t)j * nrows + r] = h;
   }
@@ -1187,11 +1291,14 @@ COBALT_API int cobalt_csv_parse(const uint8_t* buf, const int64_t* fend, int64_t
   return 0;
 }
 
+// Hashes of the string columns cols[ncols] ([ncols][nrows], 0 = missing); badq counts their fields with
+// malformed quoting (a quote inside an unquoted field, a lone quote inside a quoted one).
 COBALT_API int cobalt_csv_hash(const uint8_t* buf, const int64_t* fend, int64_t nrows, int C, const int32_t* cols,
-                               int ncols, unsigned long long* out, hipStream_t st) {
+                               int ncols, unsigned long long* out, unsigned long long* badq, hipStream_t st) {
   if (nrows <= 0 || ncols <= 0) return 0;
   if (ncols > 65535) return -1;
-  hipLaunchKernelGGL(k_csv_hash, dim3(grid_rows(nrows), ncols), dim3(256), 0, st, buf, fend, nrows, C, cols, ncols, out);
+  hipLaunchKernelGGL(k_csv_hash, dim3(grid_rows(nrows), ncols), dim3(256), 0, st, buf, fend, nrows, C, cols, ncols, out,
+                     badq);
   CK_LAUNCH();
   return 0;
 }

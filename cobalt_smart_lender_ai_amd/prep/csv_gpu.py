@@ -12,8 +12,15 @@ strings are null; a column whose non-null values all parse as numbers is numeric
 value has integer syntax and none is missing, else ``float64``); ``True``/``False`` literals make a bool
 column; anything else is a string column. Unlike pyarrow, ISO date strings stay strings (as in pandas).
 Numbers are converted exactly (see csv.hip); the rare value outside the exact fast path is re-parsed on
-the host. A file the tokenizer cannot lay out as a rectangle (ragged rows, blank lines) raises
-:class:`CsvLayoutError` and the caller falls back to pyarrow.
+the host. Like those readers, the device reads "inf" / "infinity" in any letter case, strips blanks
+(space, tab) around a number, and reads integer syntax past the int64 range as a float.
+
+The device may defer, never differ: :class:`CsvLayoutError` is raised, and the caller falls back to
+pyarrow, for a file the tokenizer cannot lay out as a rectangle (ragged rows, blank lines -- in a
+one-column file too, where pyarrow skips an empty line), for malformed quoting (a quote inside an unquoted
+field, ``"x"y``), for a hex literal (``0x10``) or a ``nan`` spelling outside pandas' list (``NAN``, ``+nan``)
+in a column that holds no other text (pyarrow reads those as numbers), and for an integer column with a
+value past 2^53, which the frame's float64 cannot hold (pyarrow's own upload refuses it too).
 """
 from __future__ import annotations
 
@@ -30,7 +37,7 @@ import torch
 
 from .. import _native
 
-ST_INT, ST_NULL, ST_TRUE, ST_FALSE, ST_STR, ST_HOST, ST_FRAC = range(7)
+ST_INT, ST_NULL, ST_TRUE, ST_FALSE, ST_STR, ST_HOST, ST_FRAC, ST_BIGINT, ST_HOSTNUM, ST_NEGZERO = range(10)
 
 _P, _I64, _I32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 _native.register("cobalt_csv_chunk", ctypes.c_int, [])
@@ -38,7 +45,7 @@ _native.register("cobalt_csv_quotes", ctypes.c_int, [_P, _I64, _P, _P])
 _native.register("cobalt_csv_delims", ctypes.c_int, [_P, _I64, _P, _P, _P])
 _native.register("cobalt_csv_fields", ctypes.c_int, [_P, _I64, _P, _P, _I32, _P, _P, _P])
 _native.register("cobalt_csv_parse", ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _I32, _P])
-_native.register("cobalt_csv_hash", ctypes.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _P])
+_native.register("cobalt_csv_hash", ctypes.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _P, _P])
 _native.register("cobalt_csv_verify", ctypes.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _P, _P])
 _native.register("cobalt_csv_span", ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P])
 _native.register("cobalt_csv_gather", ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P])
@@ -198,13 +205,18 @@ def read_csv_gpu(src, device, hash_unique_share: float = 0.2, timings: dict | No
                                stream), "cobalt_csv_fields")
     if int(bad) != 0:
         raise CsvLayoutError(f"{int(bad)} rows with a field count other than {C}")
+    if C == 1:  # every newline is a legal row end here, but the host readers skip an empty line
+        fs = torch.cat([fend.new_zeros(1), fend[:nf - 1] + 1])
+        ln = fend[:nf] - fs
+        if bool(((ln == 0) | ((ln == 1) & (buf[fs.clamp(max=n - 1)] == 0x0D))).any()):
+            raise CsvLayoutError("blank line in a one-column file")
     t_tok = time.perf_counter()
     status = torch.empty((C, N), dtype=torch.uint8, device=dev)
     vals = torch.empty((C, N), dtype=torch.float64, device=dev)
     _chk(lib.cobalt_csv_parse(buf.data_ptr(), fend.data_ptr(), N, C, status.data_ptr(), vals.data_ptr(),
                               int(pandas_fp), stream), "cobalt_csv_parse")
-    counts = torch.bincount((torch.arange(C, device=dev)[:, None] * 8 + status.long()).reshape(-1),
-                            minlength=C * 8).reshape(C, 8).cpu().numpy()
+    counts = torch.bincount((torch.arange(C, device=dev)[:, None] * 16 + status.long()).reshape(-1),
+                            minlength=C * 16).reshape(C, 16).cpu().numpy()
     t_parse = time.perf_counter()
 
     def host_reparse(c: int) -> None:
@@ -225,12 +237,16 @@ def read_csv_gpu(src, device, hash_unique_share: float = 0.2, timings: dict | No
     for c in range(C):
         cnt = counts[c]
         n_null, n_bool = cnt[ST_NULL], cnt[ST_TRUE] + cnt[ST_FALSE]
-        n_num = cnt[ST_INT] + cnt[ST_FRAC] + cnt[ST_HOST]
+        n_num = cnt[ST_INT] + cnt[ST_FRAC] + cnt[ST_HOST] + cnt[ST_BIGINT] + cnt[ST_NEGZERO]
+        if cnt[ST_HOSTNUM] and cnt[ST_STR] == 0 and n_bool == 0:  # with other text it is text to pyarrow too
+            raise CsvLayoutError(f"column {names[c]!r} holds hex or nan spellings only the host reader takes")
+        if cnt[ST_BIGINT] and cnt[ST_FRAC] == 0 and cnt[ST_HOST] == 0 and cnt[ST_STR] == 0 and n_bool == 0:
+            raise CsvLayoutError(f"integer column {names[c]!r} holds values past 2^53")
         if n_null == N:
             kinds[c] = "null"
-        elif cnt[ST_STR] == 0 and n_bool == 0:
+        elif cnt[ST_STR] + cnt[ST_HOSTNUM] == 0 and n_bool == 0:
             kinds[c] = "num"
-        elif cnt[ST_STR] == 0 and n_num == 0:
+        elif cnt[ST_STR] + cnt[ST_HOSTNUM] == 0 and n_num == 0:
             kinds[c] = "bool"
         else:
             kinds[c] = "str"
@@ -246,6 +262,9 @@ def read_csv_gpu(src, device, hash_unique_share: float = 0.2, timings: dict | No
             if cnt[ST_HOST]:
                 host_reparse(c)
             is_int = cnt[ST_FRAC] == 0 and cnt[ST_NULL] == 0 and cnt[ST_HOST] == 0
+            # "-0" is +0.0 where the host reader types the column int64, -0.0 where it parses floats
+            if cnt[ST_NEGZERO] and (cnt[ST_FRAC] or cnt[ST_HOST] or (pandas_fp and not is_int)):
+                vals[c][status[c] == ST_NEGZERO] = -0.0
             cols[name] = DCol("f", vals[c], "int64" if is_int else "float64")
         elif k == "bool":
             st = status[c]
@@ -340,13 +359,16 @@ def _string_columns(lib, stream, buf, fend, N, C, str_cols: list[int], dev, shar
     S = len(str_cols)
     cols_t = torch.tensor(str_cols, dtype=torch.int32, device=dev)
     H = torch.empty((S, N), dtype=torch.int64, device=dev)
-    _chk(lib.cobalt_csv_hash(buf.data_ptr(), fend.data_ptr(), N, C, cols_t.data_ptr(), S, H.data_ptr(), stream),
-         "cobalt_csv_hash")
+    badq = torch.zeros(1, dtype=torch.int64, device=dev)
+    _chk(lib.cobalt_csv_hash(buf.data_ptr(), fend.data_ptr(), N, C, cols_t.data_ptr(), S, H.data_ptr(),
+                             badq.data_ptr(), stream), "cobalt_csv_hash")
     valid = H != 0
     nh = min(N, 20_000)
     hs = torch.sort(H[:, :nh], dim=1).values
     distinct = (hs[:, 0] != 0).long() + ((hs[:, 1:] != hs[:, :-1]) & (hs[:, 1:] != 0)).sum(1)
     near = ((distinct > share * nh) & (N >= 1000)).cpu().tolist()
+    if int(badq):
+        raise CsvLayoutError(f"{int(badq)} fields with malformed quoting")
     out = {}
     dj = [j for j in range(S) if not near[j]]
     if dj:
