@@ -90,6 +90,24 @@ __device__ __forceinline__ int64_t wave_incl_scan(int64_t v) {
   return v;
 }
 
+template <int CTRL, int ROWM = 0xf, int BANKM = 0xf>
+__device__ __forceinline__ double dpp_f64(double v) {  // lanes without a source read 0.0
+  return __longlong_as_double(dpp64<CTRL, ROWM, BANKM>(__double_as_longlong(v), 0));
+}
+
+// Sum of doubles over the 64 lanes, valid in lane 63: the scan above, a fixed sequence of additions, so
+// the total's bits depend on the lanes' values only (no atomics, no run-to-run difference). Every lane
+// must be active.
+__device__ __forceinline__ double wave_total_f64(double v) {
+  v += dpp_f64<kDppRowShr1>(v);
+  v += dpp_f64<kDppRowShr2>(v);
+  v += dpp_f64<kDppRowShr4>(v);
+  v += dpp_f64<kDppRowShr8>(v);
+  v += dpp_f64<kDppRowBcast15, 0xa>(v);
+  v += dpp_f64<kDppRowBcast31, 0xc>(v);
+  return v;
+}
+
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll

@@ -5,46 +5,28 @@
 // trees; here each row walks the forest once, in tree order, and the metric terms are emitted after
 // every tree.
 //
-// Same packed forest and the same walk as the predictor (forest_walk.h, predict.hip k_predict): one
+// A client of the packed-forest block of forest_walk.h (ForestBlock, walk_trees), like the predictor: one
 // thread owns one row (features staged in LDS with an odd stride), tiles of the forest are staged in
 // LDS, and the margin is accumulated in fp32 in tree order -- the margin after tree t has the bits of
 // `predict_margin(n_trees = t + 1)`. After each tree the row's terms are computed in fp64 from that
 // fp32 margin m:
-//   logloss  log1p(exp(-|m|)) + max(m, 0) - y m     (from the margin: accurate for large |m|)
-//   error    (m > 0) != (y > 0.5)
-// and reduced deterministically (no floating-point atomics): the 64 lanes of a wave are summed by a
-// fixed DPP sequence, the wave's pair goes to workspace[tree][wave], and k_eval_reduce adds a tree's
+//   logloss  log1p(exp(-|m|)) + max(m, 0) - y m     (wave_partials.h logloss_term)
+//   error    (m > 0) != (y > 0.5)                   (error_term)
+// and reduced deterministically (wave_partials.h; no floating-point atomics): the 64 lanes of a wave are
+// summed by a fixed DPP sequence, the wave's pair goes to workspace[tree][wave], and k_eval_reduce adds a tree's
 // partials in a fixed order. Rows beyond kEvalChunkRows are processed in chunks of that many rows
 // (which bounds the workspace); chunk sums are added in chunk order. The same input gives the same
 // bits on every run.
 #include "common.h"
 #include "forest_walk.h"
+#include "wave_partials.h"
 #include <algorithm>
 
 using namespace cobalt;
 
 namespace {
-constexpr int kMaxTileNodes = 8192;          // as predict.hip
 constexpr int kEvalBlock = 256;
 constexpr int64_t kEvalChunkRows = 1 << 19;  // rows per launch (whole blocks): 8192 wave partials per tree
-constexpr int kReduceBlock = 256;
-
-template <int CTRL, int ROWM = 0xf, int BANKM = 0xf>
-__device__ __forceinline__ double dpp_f64(double v) {  // lanes without a source read 0.0
-  return __longlong_as_double(dpp64<CTRL, ROWM, BANKM>(__double_as_longlong(v), 0));
-}
-
-// Sum over the 64 lanes, valid in lane 63 (the DPP scan of common.h wave_incl_scan on doubles: a fixed
-// sequence of additions, so the total's bits depend on the lanes' values only). Every lane must be active.
-__device__ __forceinline__ double wave_total_f64(double v) {
-  v += dpp_f64<kDppRowShr1>(v);
-  v += dpp_f64<kDppRowShr2>(v);
-  v += dpp_f64<kDppRowShr4>(v);
-  v += dpp_f64<kDppRowShr8>(v);
-  v += dpp_f64<kDppRowBcast15, 0xa>(v);
-  v += dpp_f64<kDppRowBcast31, 0xc>(v);
-  return v;
-}
 }  // namespace
 
 // Rows [0, n) of one chunk; `stage` (nullable) points at the chunk's first row of the [n_trees, stage_ld]
@@ -58,18 +40,10 @@ __global__ __launch_bounds__(kEvalBlock) void k_eval_curve(
     const int32_t* __restrict__ tile_ptr, int n_tiles, float base_margin, const float* __restrict__ margin_in,
     float* __restrict__ margin_out, float* __restrict__ stage, int64_t stage_ld, double* __restrict__ part,
     double* __restrict__ wpart, int nparts, int tile_cap) {
-  extern __shared__ unsigned char smem[];
-  uint2* s_nodes = reinterpret_cast<uint2*>(smem);
-  float* s_x = reinterpret_cast<float*>(smem + (size_t)tile_cap * sizeof(uint2));
-  const int xs = F | 1;  // odd stride -> conflict-free LDS reads
-  const int64_t row0 = (int64_t)blockIdx.x * kEvalBlock;
-  const int64_t row = row0 + threadIdx.x;
-  const int nrows = (int)min((int64_t)kEvalBlock, n - row0);
+  const ForestBlock<kEvalBlock> fb(tile_cap, F, n);
+  const int64_t row = fb.row;
   const bool valid = row < n;
-  for (int e = threadIdx.x; e < kEvalBlock * F; e += kEvalBlock) {
-    const int r = e / F, f = e - r * F;
-    s_x[r * xs + f] = r < nrows ? X[(row0 + r) * ldx + f] : 0.0f;
-  }
+  fb.stage_rows<true>(X, F, ldx);
   float acc = (valid && margin_in) ? margin_in[row] : base_margin;
   double yv = 0.0, wv = 0.0;
   bool ypos = false;
@@ -84,21 +58,17 @@ __global__ __launch_bounds__(kEvalBlock) void k_eval_curve(
     const double sw = wave_total_f64(wv);
     if (lane_id() == kWave - 1) wpart[wave_g] = sw;
   }
-  const float* x = s_x + threadIdx.x * xs;
+  const float* x = fb.x();
   for (int tile = 0; tile < n_tiles; ++tile) {
     const int t_begin = tile_ptr[tile], t_end = tile_ptr[tile + 1];
-    const int nbase = tree_ptr[t_begin];
-    const int nn = tree_ptr[t_end] - nbase;
-    __syncthreads();
-    for (int i = threadIdx.x; i < nn; i += kEvalBlock) s_nodes[i] = nodes[nbase + i];
-    __syncthreads();
-    walk_trees(s_nodes, tree_ptr, nbase, t_begin, t_end, x, [&](int t, float v) {
+    const int nbase = fb.stage_tile(nodes, tree_ptr, t_begin, t_end);
+    walk_trees(fb.s_nodes, tree_ptr, nbase, t_begin, t_end, x, [&](int t, float v, uint32_t) {
       acc += v;
       if (stage && valid) stage[(int64_t)t * stage_ld + row] = acc;
       if constexpr (METRICS) {
         const double m = (double)acc;
-        const double loss = log1p(exp(-fabs(m))) + fmax(m, 0.0) - yv * m;
-        const double err = ((acc > 0.0f) != ypos) ? 1.0 : 0.0;
+        const double loss = logloss_term(m, yv);
+        const double err = error_term(acc, ypos);
         const double sl = wave_total_f64(wv * loss);
         const double se = wave_total_f64(wv * err);
         if (lane_id() == kWave - 1) {
@@ -143,18 +113,13 @@ __global__ __launch_bounds__(kReduceBlock) void k_eval_reduce(const double* __re
   if (tid < 3) sums[t * 3 + tid] = (accumulate ? sums[t * 3 + tid] : 0.0) + s[tid][0];
 }
 
-// Wave partials of one launch over n rows: every wave of every block writes one (the last block's waves
-// past the rows write zeros).
-static int64_t eval_parts(int64_t n) {
-  return (std::min(n, kEvalChunkRows) + kEvalBlock - 1) / kEvalBlock * (kEvalBlock / kWave);
-}
+static int64_t eval_parts(int64_t n) { return wave_parts(n, kEvalChunkRows, kEvalBlock); }
 
 // Bytes of `workspace` for n rows and n_trees trees: [n_trees][parts][2] + [parts] doubles with
 // parts = the waves of one row chunk.
 COBALT_API int64_t cobalt_eval_curve_workspace(int64_t n, int n_trees) {
   if (n <= 0 || n_trees <= 0) return 0;
-  const int64_t parts = eval_parts(n);
-  return ((int64_t)n_trees * parts * 2 + parts) * (int64_t)sizeof(double);
+  return wave_partials_bytes(n_trees, eval_parts(n));
 }
 
 // y == nullptr: no metrics (margins / stage margins only; w, workspace and sums are not touched).
@@ -166,21 +131,17 @@ COBALT_API int cobalt_eval_curve(const float* X, int64_t n, int F, int64_t ldx, 
                                  float* margin_out, float* stage_margins, void* workspace, double* sums,
                                  hipStream_t stream) {
   if (n <= 0 || n_trees <= 0) return 0;
-  if (tile_cap < 1 || tile_cap > kMaxTileNodes) return -2;
-  const size_t lds = (size_t)tile_cap * sizeof(uint2) + (size_t)kEvalBlock * (F | 1) * sizeof(float);
-  if (lds > 160 * 1024) return -3;
+  if (const int rc = forest_limits(tile_cap, F, kEvalBlock)) return rc;
+  const size_t lds = forest_lds_bytes(tile_cap, F, kEvalBlock);
   const bool metrics = y != nullptr;
   if (metrics && (workspace == nullptr || sums == nullptr)) return -7;
   const void* fn = metrics ? (const void*)k_eval_curve<true> : (const void*)k_eval_curve<false>;
-  static size_t attr_set[2] = {64 * 1024, 64 * 1024};
-  if (lds > attr_set[metrics]) {
-    CK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set[metrics] = lds;
-  }
+  static size_t attr_set[2] = {kDefaultMaxLds, kDefaultMaxLds};
+  CK(raise_dynamic_lds(fn, lds, attr_set[metrics]));
   const uint2* nd = static_cast<const uint2*>(nodes);
   const int nparts = (int)eval_parts(n);
   double* part = static_cast<double*>(workspace);
-  double* wpart = part ? part + (int64_t)n_trees * nparts * 2 : nullptr;
+  double* wpart = wave_wpart(part, n_trees, nparts);
   for (int64_t r0 = 0; r0 < n; r0 += kEvalChunkRows) {
     const int64_t nc = std::min(kEvalChunkRows, n - r0);
     const int grid = ceil_div(nc, kEvalBlock);

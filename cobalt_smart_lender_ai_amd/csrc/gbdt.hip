@@ -24,6 +24,7 @@
 //    histogram slots per level, issued on the same stream through a native RCCL communicator.
 #include "common.h"
 #include "comm.h"
+#include "gbdt_math.h"
 #include "ipc_device.h"
 #include "knobs.h"
 #include <math.h>
@@ -361,33 +362,7 @@ __global__ __launch_bounds__(256) void k_bin(const float* __restrict__ X, int64_
 // ------------------------------------------------------------------------------------------
 // Per-tree initialisation + binary:logistic gradients (K14)
 // ------------------------------------------------------------------------------------------
-// Gradient fixed point (models/gbdt_host.py gradients_host is the oracle): |g| <= w_max and
-// h <= w_max / 4 are scaled to 17 bits and rounded UNBIASED, q = floor(x * scale + u) with u ~ U[0,1)
-// drawn from a per-(tree, global row) hash -- E[q] = x * scale, so small hessians are not flushed
-// to 0 and rounding errors of histogram sums average out instead of accumulating a bias. The draw is
-// deterministic (same trees on every device and rank count). Bounds: a <= 16384-row histogram block
-// sums to |sum g| < 2^31 and sum h <= 2^31, so the packed u64 (signed g high, h low) never carries.
-// Wide gradients (GbdtConfig::grad_bits 25): 25-bit magnitudes, summed in int64 cells (a 16384-row block
-// < 2^39; 10M rows < 2^49, exact in the host oracle's float64 sums too).
-constexpr int64_t kGClip = (1 << 17) - 1, kHClip = 1 << 17;
-constexpr int64_t kGClipW = (1 << 25) - 1, kHClipW = 1 << 25;
-constexpr uint64_t kDitherSalt = 0xD1B54A32D192ED03ull;
-
-__device__ __forceinline__ uint64_t tree_key_of(uint64_t seed, int tree) {
-  return splitmix64(seed ^ (0xA5A5A5A5ull + (uint64_t)tree * 0x632BE59BD9B4E019ull));
-}
-
-__device__ __forceinline__ void quantize_gh(double g, double h, double gscale, double hscale, uint64_t dkey,
-                                            int64_t grow, int64_t& gq, int64_t& hq, bool wide = false) {
-  const uint64_t r = splitmix64(dkey ^ (uint64_t)grow);
-  const double ug = (double)(uint32_t)(r >> 32) * (1.0 / 4294967296.0);
-  const double uh = (double)(uint32_t)r * (1.0 / 4294967296.0);
-  gq = (int64_t)floor(g * gscale + ug);
-  hq = (int64_t)floor(h * hscale + uh);
-  const int64_t gc = wide ? kGClipW : kGClip, hc = wide ? kHClipW : kHClip;
-  gq = gq > gc ? gc : (gq < -gc ? -gc : gq);
-  hq = hq > hc ? hc : (hq < 0 ? 0 : hq);
-}
+// The gradient fixed point (kGClip.., tree_key_of, quantize_gh): gbdt_math.h
 // Reset the node table of a new tree (root active with all local rows) and the per-node counters.
 __device__ void init_tree_block(const GbdtDev& d) {
   for (int i = threadIdx.x; i < d.max_nodes; i += blockDim.x) {
@@ -1561,17 +1536,7 @@ __global__ __launch_bounds__(256) void k_hist_reduce(GbdtDev d, int parity, int 
 // Split evaluation (K16 + K17): one block per node of the level, one wavefront per feature,
 // 4 bins per lane, 64-lane int64 prefix scan, both default directions.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ double thresh_l1(double g, double alpha) {
-  if (g > alpha) return g - alpha;
-  if (g < -alpha) return g + alpha;
-  return 0.0;
-}
-
-__device__ __forceinline__ double calc_gain(double g, double h, double lambda_, double alpha, double mcw) {
-  if (h < mcw) return 0.0;
-  const double t = alpha == 0.0 ? g : thresh_l1(g, alpha);
-  return (t * t) / (h + lambda_);
-}
+// thresh_l1 / calc_gain / calc_weight: gbdt_math.h
 
 // Both children's gains of a candidate split with ONE fp64 division: (tl^2 (hr + lambda) + tr^2 (hl +
 // lambda)) / ((hl + lambda)(hr + lambda)). Candidates are only scored when both children reach
@@ -1582,12 +1547,6 @@ __device__ __forceinline__ double calc_gain_pair(double gl, double hl, double gr
   const double tr = alpha == 0.0 ? gr : thresh_l1(gr, alpha);
   const double dl = hl + lambda_, dr = hr + lambda_;
   return (tl * tl * dr + tr * tr * dl) / (dl * dr);
-}
-
-__device__ __forceinline__ double calc_weight(double g, double h, double lambda_, double alpha, double mcw) {
-  if (h < mcw || h <= 0.0) return 0.0;
-  const double t = alpha == 0.0 ? g : thresh_l1(g, alpha);
-  return -t / (h + lambda_);
 }
 
 // Monotone constraints (constrained mode; models/gbdt_host.py _eval_node_mono is the specification).

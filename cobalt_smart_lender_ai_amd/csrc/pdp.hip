@@ -2,8 +2,8 @@
 // features (gfx950): every row is scored at every grid point with x[f1] (and x[f2]) replaced by the grid
 // point's value, and the margins / probabilities are averaged per grid point.
 //
-// Third client of the packed forest (forest_walk.h) after predict.hip and evalcurve.hip, with the structure
-// of evalcurve.hip: one thread owns one row (features staged in LDS with the odd stride F | 1), tiles of the
+// A client of the packed-forest block of forest_walk.h (ForestBlock): one thread owns one row (features
+// staged in LDS with the odd stride F | 1, rows past n as zeros), tiles of the
 // forest are staged in LDS, leaf values are added in fp32 in tree order starting from base_margin. Grid point
 // k = i1 * G2 + i2 scores x[f1] = g1[i1], x[f2] = g2[i2] (f2 = -1: 1-D, G2 = 1); a NaN grid value is the
 // "feature missing" point and takes the trees' default directions. ice[k][r] has the bits of predict_margin
@@ -18,7 +18,6 @@
 //    point again; nothing is written for them.
 //  * The kWalk = 4 chains that overlap their dependent LDS reads are 4 grid points of one tree
 //    (pdp_walk.h walk_tree_grid); the trees are visited in order, so each point's sum keeps the tree order.
-//    forest_walk.h and predict.hip are untouched.
 //  * The grid values of a chunk are the same in every lane: they are loaded once per block, the first axis
 //    into scalar registers (16 SGPRs). The kernel is instantiated for 1-D (one compare per split) and 2-D (two
 //    compares; the second axis' 16 values are pinned to vector registers, since 32 SGPRs of grid values made
@@ -26,41 +25,23 @@
 //  * No "tree ignores f1 / f2" shortcut: it was not measured, so it is not there.
 //  * PD sums: per grid point sum w m and sum w p with m the fp32 margin widened to double and
 //    p = 1 / (1 + exp(-m)) in double; the 64 lanes of a wave are summed by a fixed DPP sequence, the wave's
-//    pair goes to workspace[point][wave], and k_pdp_reduce adds a point's partials in a fixed order. No
+//    pair goes to workspace[point][wave], and k_pair_reduce (wave_partials.h) adds a point's partials in a fixed order. No
 //    floating-point atomics: the same input gives the same bits on every run. Rows past n in the last block
 //    walk a row of zeros and enter the wave sums as the constant 0.0.
 //  * Rows are processed in chunks of kPdpChunkRows = 2^17 (2048 wave partials per grid point, which bounds
 //    the workspace: 32 KiB per grid point); chunk sums are added in chunk order.
 #include "common.h"
 #include "pdp_walk.h"
+#include "wave_partials.h"
 #include <algorithm>
 
 using namespace cobalt;
 
 namespace {
-constexpr int kMaxTileNodes = 8192;  // as predict.hip
 constexpr int kPdpBlock = 256;
 constexpr int kGridChunk = 16;
 constexpr int64_t kPdpChunkRows = 1 << 17;
 constexpr int kPdpMaxGrid = 1 << 16;  // grid points per call (gridDim.y = points / kGridChunk <= 4096)
-constexpr int kReduceBlock = 256;
-
-template <int CTRL, int ROWM = 0xf, int BANKM = 0xf>
-__device__ __forceinline__ double dpp_f64(double v) {  // lanes without a source read 0.0
-  return __longlong_as_double(dpp64<CTRL, ROWM, BANKM>(__double_as_longlong(v), 0));
-}
-
-// Sum over the 64 lanes, valid in lane 63: a fixed sequence of additions (as evalcurve.hip). Every lane
-// must be active.
-__device__ __forceinline__ double wave_total_f64(double v) {
-  v += dpp_f64<kDppRowShr1>(v);
-  v += dpp_f64<kDppRowShr2>(v);
-  v += dpp_f64<kDppRowShr4>(v);
-  v += dpp_f64<kDppRowShr8>(v);
-  v += dpp_f64<kDppRowBcast15, 0xa>(v);
-  v += dpp_f64<kDppRowBcast31, 0xc>(v);
-  return v;
-}
 }  // namespace
 
 // Rows [0, n) of one row chunk (blockIdx.x) at the grid points [blockIdx.y * kGridChunk, + kGridChunk).
@@ -76,18 +57,10 @@ __global__ __launch_bounds__(kPdpBlock) void k_pdp(const float* __restrict__ X, 
                                                    const float* __restrict__ g2, int G2, int G,
                                                    float* __restrict__ ice, int64_t ice_ld, double* __restrict__ part,
                                                    double* __restrict__ wpart, int nparts, int tile_cap) {
-  extern __shared__ unsigned char smem[];
-  uint2* s_nodes = reinterpret_cast<uint2*>(smem);
-  float* s_x = reinterpret_cast<float*>(smem + (size_t)tile_cap * sizeof(uint2));
-  const int xs = F | 1;  // odd stride -> conflict-free LDS reads
-  const int64_t row0 = (int64_t)blockIdx.x * kPdpBlock;
-  const int64_t row = row0 + threadIdx.x;
-  const int nrows = (int)min((int64_t)kPdpBlock, n - row0);
+  const ForestBlock<kPdpBlock> fb(tile_cap, F, n);
+  const int64_t row = fb.row;
   const bool valid = row < n;
-  for (int e = threadIdx.x; e < kPdpBlock * F; e += kPdpBlock) {
-    const int r = e / F, f = e - r * F;
-    s_x[r * xs + f] = r < nrows ? X[(row0 + r) * ldx + f] : 0.0f;
-  }
+  fb.stage_rows<true>(X, F, ldx);
   // the chunk's grid values (block-uniform); points past G repeat the last one
   const int k0 = blockIdx.y * kGridChunk;
   GridVec<kGridChunk> v1, v2, acc;
@@ -104,16 +77,12 @@ __global__ __launch_bounds__(kPdpBlock) void k_pdp(const float* __restrict__ X, 
     v2[j] = b;
     acc[j] = base_margin;
   }
-  const float* x = s_x + threadIdx.x * xs;
+  const float* x = fb.x();
   for (int tile = 0; tile < n_tiles; ++tile) {
     const int t_begin = tile_ptr[tile], t_end = tile_ptr[tile + 1];
-    const int nbase = tree_ptr[t_begin];
-    const int nn = tree_ptr[t_end] - nbase;
-    __syncthreads();
-    for (int i = threadIdx.x; i < nn; i += kPdpBlock) s_nodes[i] = nodes[nbase + i];
-    __syncthreads();
+    const int nbase = fb.stage_tile(nodes, tree_ptr, t_begin, t_end);
     for (int t = t_begin; t < t_end; ++t)
-      walk_tree_grid<kGridChunk, TWO>(s_nodes, (uint32_t)(tree_ptr[t] - nbase), x, f1, f2, v1, v2, acc);
+      walk_tree_grid<kGridChunk, TWO>(fb.s_nodes, (uint32_t)(tree_ptr[t] - nbase), x, f1, f2, v1, v2, acc);
   }
   if (ice && valid) {
 #pragma unroll
@@ -142,45 +111,7 @@ __global__ __launch_bounds__(kPdpBlock) void k_pdp(const float* __restrict__ X, 
   }
 }
 
-// Block k < G: thread i adds the partials i, i + 256, ... (< np) of grid point k in index order, then the 256
-// thread sums are combined by a fixed LDS tree -> sums[k][0..1]. Block G does the same for wpart ->
-// sums[2 G] (sum w). `accumulate`: add this row chunk's sums to the earlier chunks' (chunk order).
-__global__ __launch_bounds__(kReduceBlock) void k_pdp_reduce(const double* __restrict__ part,
-                                                             const double* __restrict__ wpart, int pitch, int np,
-                                                             int G, double* __restrict__ sums, int accumulate) {
-  __shared__ double s[2][kReduceBlock];
-  const int k = blockIdx.x, tid = threadIdx.x;
-  double a = 0.0, b = 0.0;
-  if (k < G) {
-    const double* src = part + (int64_t)k * pitch * 2;
-    for (int i = tid; i < np; i += kReduceBlock) {
-      a += src[2 * i];
-      b += src[2 * i + 1];
-    }
-  } else {
-    for (int i = tid; i < np; i += kReduceBlock) a += wpart[i];
-  }
-  s[0][tid] = a;
-  s[1][tid] = b;
-  __syncthreads();
-  for (int o = kReduceBlock / 2; o > 0; o >>= 1) {
-    if (tid < o) {
-      s[0][tid] += s[0][tid + o];
-      s[1][tid] += s[1][tid + o];
-    }
-    __syncthreads();
-  }
-  if (k < G) {
-    if (tid < 2) sums[2 * k + tid] = (accumulate ? sums[2 * k + tid] : 0.0) + s[tid][0];
-  } else if (tid == 0) {
-    sums[2 * (int64_t)G] = (accumulate ? sums[2 * (int64_t)G] : 0.0) + s[0][0];
-  }
-}
-
-// Wave partials of one launch over n rows (every wave of every block writes one).
-static int64_t pdp_parts(int64_t n) {
-  return (std::min(n, kPdpChunkRows) + kPdpBlock - 1) / kPdpBlock * (kPdpBlock / kWave);
-}
+static int64_t pdp_parts(int64_t n) { return wave_parts(n, kPdpChunkRows, kPdpBlock); }
 
 COBALT_API int cobalt_pdp_grid_chunk() { return kGridChunk; }
 COBALT_API int64_t cobalt_pdp_chunk_rows() { return kPdpChunkRows; }
@@ -190,8 +121,7 @@ COBALT_API int cobalt_pdp_max_grid() { return kPdpMaxGrid; }
 // waves of one row chunk.
 COBALT_API int64_t cobalt_pdp_workspace(int64_t n, int G) {
   if (n <= 0 || G <= 0) return 0;
-  const int64_t parts = pdp_parts(n);
-  return ((int64_t)G * parts * 2 + parts) * (int64_t)sizeof(double);
+  return wave_partials_bytes(G, pdp_parts(n));
 }
 
 // ice: [G1 * G2, n] float32 margins or nullptr; sums: [2 G + 1] doubles (sum w m, sum w p per grid point,
@@ -205,9 +135,8 @@ COBALT_API int cobalt_pdp(const float* X, int64_t n, int F, int64_t ldx, const v
   if (F < 1 || f1 < 0 || f1 >= F || f2 < -1 || f2 >= F || f2 == f1 || g1 == nullptr || G1 < 1 || G2 < 1) return -8;
   if (f2 < 0 ? G2 != 1 : g2 == nullptr) return -8;
   if ((int64_t)G1 * G2 > kPdpMaxGrid) return -8;
-  if (tile_cap < 1 || tile_cap > kMaxTileNodes) return -2;
-  const size_t lds = (size_t)tile_cap * sizeof(uint2) + (size_t)kPdpBlock * (F | 1) * sizeof(float);
-  if (lds > 160 * 1024) return -3;
+  if (const int rc = forest_limits(tile_cap, F, kPdpBlock)) return rc;
+  const size_t lds = forest_lds_bytes(tile_cap, F, kPdpBlock);
   const bool want_sums = sums != nullptr;
   if (want_sums && workspace == nullptr) return -7;
   if (n <= 0 || (ice == nullptr && !want_sums)) return 0;
@@ -215,16 +144,13 @@ COBALT_API int cobalt_pdp(const float* X, int64_t n, int F, int64_t ldx, const v
   static const Kernel kernels[4] = {k_pdp<false, false>, k_pdp<false, true>, k_pdp<true, false>, k_pdp<true, true>};
   const int which = (want_sums ? 2 : 0) + (f2 >= 0 ? 1 : 0);
   const Kernel fn = kernels[which];
-  static size_t attr_set[4] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
-  if (lds > attr_set[which]) {
-    CK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set[which] = lds;
-  }
+  static size_t attr_set[4] = {kDefaultMaxLds, kDefaultMaxLds, kDefaultMaxLds, kDefaultMaxLds};
+  CK(raise_dynamic_lds((const void*)fn, lds, attr_set[which]));
   const uint2* nd = static_cast<const uint2*>(nodes);
   const int G = G1 * G2;
   const int nparts = (int)pdp_parts(n);
   double* part = want_sums ? static_cast<double*>(workspace) : nullptr;
-  double* wpart = part ? part + (int64_t)G * nparts * 2 : nullptr;
+  double* wpart = wave_wpart(part, G, nparts);
   const dim3 block(kPdpBlock);
   for (int64_t r0 = 0; r0 < n; r0 += kPdpChunkRows) {
     const int64_t nc = std::min(kPdpChunkRows, n - r0);
@@ -234,7 +160,7 @@ COBALT_API int cobalt_pdp(const float* X, int64_t n, int F, int64_t ldx, const v
                        part, wpart, nparts, tile_cap);
     CK_LAUNCH();
     if (want_sums) {
-      hipLaunchKernelGGL(k_pdp_reduce, dim3(G + 1), dim3(kReduceBlock), 0, stream, part, wpart, nparts,
+      hipLaunchKernelGGL(k_pair_reduce<>, dim3(G + 1), dim3(kReduceBlock), 0, stream, part, wpart, nparts,
                          (int)pdp_parts(nc), G, sums, r0 > 0 ? 1 : 0);
       CK_LAUNCH();
     }

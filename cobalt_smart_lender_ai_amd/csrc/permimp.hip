@@ -2,7 +2,7 @@
 // replaced by cols[i][perm[r][n]] (the column's value of another row) and reduces the logloss / error terms
 // of the job's margins; job 0, the baseline, substitutes nothing.
 //
-// Fourth client of the packed forest (forest_walk.h) with the structure of pdp.hip: one thread owns one row
+// A client of the packed-forest block of forest_walk.h (ForestBlock), like pdp.hip: one thread owns one row
 // (features staged in LDS with the odd stride F | 1), tiles of the forest are staged in LDS, leaf values are
 // added in fp32 in tree order starting from base_margin, so margins[job][n] has the bits of predict_margin on
 // the substituted matrix. The substitution is the select of pdp_walk.h on the value read from LDS: neither X
@@ -23,42 +23,24 @@
 //    the live repeats keep base_margin and are never written. `live` is block-uniform.
 //  * No "tree does not use f1" shortcut: it was not measured, so it is not there.
 //  * Sums: per job sum w loss and sum w err with, in fp64 from the fp32 margin m, loss = log1p(exp(-|m|)) +
-//    max(m, 0) - y m and err = (m > 0) != (y > 0.5) (the terms of evalcurve.hip); the 64 lanes of a wave are
-//    summed by a fixed DPP sequence, the wave's pair goes to workspace[job][wave], and k_perm_reduce adds a
+//    max(m, 0) - y m and err = (m > 0) != (y > 0.5) (wave_partials.h, as evalcurve.hip); the 64 lanes of a wave
+//    are summed by a fixed DPP sequence, the wave's pair goes to workspace[job][wave], and k_pair_reduce adds a
 //    job's partials in a fixed order. No floating-point atomics: the same input gives the same bits on every
 //    run. Rows past n in the last block walk a row of zeros with weight 0.0 and take part in every wave sum.
 //  * Rows are processed in chunks of kPermChunkRows = 2^17 (2048 wave partials per job: 32 KiB of workspace
 //    per job); chunk sums are added in chunk order.
 #include "common.h"
 #include "pdp_walk.h"
+#include "wave_partials.h"
 #include <algorithm>
 
 using namespace cobalt;
 
 namespace {
-constexpr int kMaxTileNodes = 8192;  // as predict.hip
 constexpr int kPermBlock = 256;
 constexpr int kPermRepChunk = 16;    // default repeats per block (8 is also built; measured in docs/PERF.md)
 constexpr int64_t kPermChunkRows = 1 << 17;
 constexpr int kPermMaxJobs = 1 << 20;
-constexpr int kReduceBlock = 256;
-
-template <int CTRL, int ROWM = 0xf, int BANKM = 0xf>
-__device__ __forceinline__ double dpp_f64(double v) {  // lanes without a source read 0.0
-  return __longlong_as_double(dpp64<CTRL, ROWM, BANKM>(__double_as_longlong(v), 0));
-}
-
-// Sum over the 64 lanes, valid in lane 63: a fixed sequence of additions (as evalcurve.hip). Every lane
-// must be active.
-__device__ __forceinline__ double wave_total_f64(double v) {
-  v += dpp_f64<kDppRowShr1>(v);
-  v += dpp_f64<kDppRowShr2>(v);
-  v += dpp_f64<kDppRowShr4>(v);
-  v += dpp_f64<kDppRowShr8>(v);
-  v += dpp_f64<kDppRowBcast15, 0xa>(v);
-  v += dpp_f64<kDppRowBcast31, 0xc>(v);
-  return v;
-}
 
 // One tree for the repeats [0, live) of the chunk: groups of kWalk chains, then one group of live % kWalk.
 // `live` is the same in every lane of the block.
@@ -92,18 +74,10 @@ __global__ __launch_bounds__(kPermBlock) void k_permimp(
     const int32_t* __restrict__ tile_ptr, int n_tiles, float base_margin, const int32_t* __restrict__ feats,
     const float* __restrict__ cols, const int32_t* __restrict__ perm, int R, int64_t ldn,
     float* __restrict__ margins, double* __restrict__ part, double* __restrict__ wpart, int nparts, int tile_cap) {
-  extern __shared__ unsigned char smem[];
-  uint2* s_nodes = reinterpret_cast<uint2*>(smem);
-  float* s_x = reinterpret_cast<float*>(smem + (size_t)tile_cap * sizeof(uint2));
-  const int xs = F | 1;  // odd stride -> conflict-free LDS reads
-  const int64_t row0 = (int64_t)blockIdx.x * kPermBlock;
-  const int64_t row = row0 + threadIdx.x;
-  const int nrows = (int)min((int64_t)kPermBlock, n - row0);
+  const ForestBlock<kPermBlock> fb(tile_cap, F, n);
+  const int64_t row = fb.row;
   const bool valid = row < n;
-  for (int e = threadIdx.x; e < kPermBlock * F; e += kPermBlock) {
-    const int r = e / F, f = e - r * F;
-    s_x[r * xs + f] = r < nrows ? X[(row0 + r) * ldx + f] : 0.0f;
-  }
+  fb.stage_rows<true>(X, F, ldx);
   // the block's jobs (block-uniform): the baseline, or `live` repeats of one feature slot from repeat k0 on
   const int rep_chunks = (R + kChunk - 1) / kChunk;
   int f1 = -1, k0 = 0, live = 1, job0 = 0;
@@ -123,16 +97,12 @@ __global__ __launch_bounds__(kPermBlock) void k_permimp(
     v[j] = a;
     acc[j] = base_margin;
   }
-  const float* x = s_x + threadIdx.x * xs;
+  const float* x = fb.x();
   for (int tile = 0; tile < n_tiles; ++tile) {
     const int t_begin = tile_ptr[tile], t_end = tile_ptr[tile + 1];
-    const int nbase = tree_ptr[t_begin];
-    const int nn = tree_ptr[t_end] - nbase;
-    __syncthreads();
-    for (int i = threadIdx.x; i < nn; i += kPermBlock) s_nodes[i] = nodes[nbase + i];
-    __syncthreads();
+    const int nbase = fb.stage_tile(nodes, tree_ptr, t_begin, t_end);
     for (int t = t_begin; t < t_end; ++t)
-      walk_tree_live<kChunk>(s_nodes, (uint32_t)(tree_ptr[t] - nbase), x, f1, live, v, acc);
+      walk_tree_live<kChunk>(fb.s_nodes, (uint32_t)(tree_ptr[t] - nbase), x, f1, live, v, acc);
   }
   if (margins && valid) {
 #pragma unroll
@@ -157,8 +127,8 @@ __global__ __launch_bounds__(kPermBlock) void k_permimp(
     for (int j = 0; j < kChunk; ++j) {
       if (j < live) {
         const double m = (double)acc[j];
-        const double loss = log1p(exp(-fabs(m))) + fmax(m, 0.0) - yv * m;
-        const double err = ((acc[j] > 0.0f) != ypos) ? 1.0 : 0.0;
+        const double loss = logloss_term(m, yv);
+        const double err = error_term(acc[j], ypos);
         const double sl = wave_total_f64(valid ? wv * loss : 0.0);
         const double se = wave_total_f64(valid ? wv * err : 0.0);
         if (lane_id() == kWave - 1) {
@@ -171,45 +141,7 @@ __global__ __launch_bounds__(kPermBlock) void k_permimp(
   }
 }
 
-// Block k < J: thread i adds the partials i, i + 256, ... (< np) of job k in index order, then the 256 thread
-// sums are combined by a fixed LDS tree -> sums[2 k + 0..1]. Block J does the same for wpart -> sums[2 J]
-// (sum w). `accumulate`: add this row chunk's sums to the earlier chunks' (chunk order).
-__global__ __launch_bounds__(kReduceBlock) void k_perm_reduce(const double* __restrict__ part,
-                                                              const double* __restrict__ wpart, int pitch, int np,
-                                                              int J, double* __restrict__ sums, int accumulate) {
-  __shared__ double s[2][kReduceBlock];
-  const int k = blockIdx.x, tid = threadIdx.x;
-  double a = 0.0, b = 0.0;
-  if (k < J) {
-    const double* src = part + (int64_t)k * pitch * 2;
-    for (int i = tid; i < np; i += kReduceBlock) {
-      a += src[2 * i];
-      b += src[2 * i + 1];
-    }
-  } else {
-    for (int i = tid; i < np; i += kReduceBlock) a += wpart[i];
-  }
-  s[0][tid] = a;
-  s[1][tid] = b;
-  __syncthreads();
-  for (int o = kReduceBlock / 2; o > 0; o >>= 1) {
-    if (tid < o) {
-      s[0][tid] += s[0][tid + o];
-      s[1][tid] += s[1][tid + o];
-    }
-    __syncthreads();
-  }
-  if (k < J) {
-    if (tid < 2) sums[2 * (int64_t)k + tid] = (accumulate ? sums[2 * (int64_t)k + tid] : 0.0) + s[tid][0];
-  } else if (tid == 0) {
-    sums[2 * (int64_t)J] = (accumulate ? sums[2 * (int64_t)J] : 0.0) + s[0][0];
-  }
-}
-
-// Wave partials of one launch over n rows (every wave of every block writes one).
-static int64_t perm_parts(int64_t n) {
-  return (std::min(n, kPermChunkRows) + kPermBlock - 1) / kPermBlock * (kPermBlock / kWave);
-}
+static int64_t perm_parts(int64_t n) { return wave_parts(n, kPermChunkRows, kPermBlock); }
 
 COBALT_API int cobalt_perm_rep_chunk() { return kPermRepChunk; }
 COBALT_API int64_t cobalt_perm_chunk_rows() { return kPermChunkRows; }
@@ -218,8 +150,7 @@ COBALT_API int64_t cobalt_perm_chunk_rows() { return kPermChunkRows; }
 // parts = the waves of one row chunk.
 COBALT_API int64_t cobalt_perm_workspace(int64_t n, int jobs) {
   if (n <= 0 || jobs <= 0) return 0;
-  const int64_t parts = perm_parts(n);
-  return ((int64_t)jobs * parts * 2 + parts) * (int64_t)sizeof(double);
+  return wave_partials_bytes(jobs, perm_parts(n));
 }
 
 // Jobs: 0 = the baseline, 1 + i * R + r = feature slot i under perm[r]. feats: nf int32 ON THE DEVICE, each in
@@ -242,9 +173,8 @@ COBALT_API int cobalt_perm_importance(const float* X, int64_t n, int F, int64_t 
   if ((int64_t)nf * R + 1 > kPermMaxJobs || (int64_t)nf * ceil_div(R, rep_chunk) + 1 > 65535) return -8;
   const bool want_sums = sums != nullptr;
   if (want_sums && y == nullptr) return -8;
-  if (tile_cap < 1 || tile_cap > kMaxTileNodes) return -2;
-  const size_t lds = (size_t)tile_cap * sizeof(uint2) + (size_t)kPermBlock * (F | 1) * sizeof(float);
-  if (lds > 160 * 1024) return -3;
+  if (const int rc = forest_limits(tile_cap, F, kPermBlock)) return rc;
+  const size_t lds = forest_lds_bytes(tile_cap, F, kPermBlock);
   if (want_sums && workspace == nullptr) return -7;
   if (n == 0 || (margins == nullptr && !want_sums)) return 0;
   using Kernel = decltype(&k_permimp<false, 8>);
@@ -252,16 +182,13 @@ COBALT_API int cobalt_perm_importance(const float* X, int64_t n, int F, int64_t 
                                     k_permimp<true, 16>};
   const int which = (want_sums ? 2 : 0) + (rep_chunk == 16 ? 1 : 0);
   const Kernel fn = kernels[which];
-  static size_t attr_set[4] = {64 * 1024, 64 * 1024, 64 * 1024, 64 * 1024};
-  if (lds > attr_set[which]) {
-    CK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set[which] = lds;
-  }
+  static size_t attr_set[4] = {kDefaultMaxLds, kDefaultMaxLds, kDefaultMaxLds, kDefaultMaxLds};
+  CK(raise_dynamic_lds((const void*)fn, lds, attr_set[which]));
   const uint2* nd = static_cast<const uint2*>(nodes);
   const int J = 1 + nf * R;
   const int nparts = (int)perm_parts(n);
   double* part = want_sums ? static_cast<double*>(workspace) : nullptr;
-  double* wpart = part ? part + (int64_t)J * nparts * 2 : nullptr;
+  double* wpart = wave_wpart(part, J, nparts);
   const dim3 block(kPermBlock);
   for (int64_t r0 = 0; r0 < n; r0 += kPermChunkRows) {
     const int64_t nc = std::min(kPermChunkRows, n - r0);
@@ -272,7 +199,7 @@ COBALT_API int cobalt_perm_importance(const float* X, int64_t n, int F, int64_t 
                        tile_cap);
     CK_LAUNCH();
     if (want_sums) {
-      hipLaunchKernelGGL(k_perm_reduce, dim3(J + 1), dim3(kReduceBlock), 0, stream, part, wpart, nparts,
+      hipLaunchKernelGGL(k_pair_reduce<>, dim3(J + 1), dim3(kReduceBlock), 0, stream, part, wpart, nparts,
                          (int)perm_parts(nc), J, sums, r0 > 0 ? 1 : 0);
       CK_LAUNCH();
     }

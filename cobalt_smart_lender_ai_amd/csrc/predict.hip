@@ -24,16 +24,9 @@
 
 using namespace cobalt;
 
-namespace {
-// LDS tile capacity (nodes) is chosen per model by the host packer (ops/predict_ops.py
-// pack_forest: 2048 unless one tree is larger) and passed to the launch. Small tiles keep the
-// per-block LDS footprint low -> more resident blocks per CU, which is what bounds this
-// latency-bound walk: 125M-row scoring went 490M (6144-node tiles) -> 810M rows/s (2048).
-constexpr int kMaxTileNodes = 8192;
-}
-
 // ------------------------------------------------------------------------------------ predictor
-// walk_trees (kWalk trees per thread at once, leaf values delivered in tree order): forest_walk.h
+// ForestBlock (row / tile staging), walk_trees (kWalk trees per thread at once, leaf values delivered in
+// tree order) and the tile / LDS limits: forest_walk.h
 
 template <int W>
 __global__ __launch_bounds__(256) void k_predict(const float* __restrict__ X, int64_t n, int F, int64_t ldx,
@@ -41,32 +34,18 @@ __global__ __launch_bounds__(256) void k_predict(const float* __restrict__ X, in
                                                  const int32_t* __restrict__ tile_ptr, int n_tiles, float base_margin,
                                                  float* __restrict__ out_margin, float* __restrict__ out_prob,
                                                  int tile_cap) {
-  extern __shared__ unsigned char smem[];
-  uint2* s_nodes = reinterpret_cast<uint2*>(smem);
-  float* s_x = reinterpret_cast<float*>(smem + (size_t)tile_cap * sizeof(uint2));
-  const int xs = F | 1;  // odd stride -> conflict-free LDS reads
-  const int64_t row0 = (int64_t)blockIdx.x * blockDim.x;
-  const int64_t row = row0 + threadIdx.x;
-  const int nrows = (int)min((int64_t)blockDim.x, n - row0);
-  // stage the block's rows (coalesced over the contiguous [nrows][F] slab when ldx == F)
-  for (int e = threadIdx.x; e < nrows * F; e += blockDim.x) {
-    const int r = e / F, f = e - r * F;
-    s_x[r * xs + f] = X[(row0 + r) * ldx + f];
-  }
+  const ForestBlock<> fb(tile_cap, F, n);
+  fb.stage_rows<false>(X, F, ldx);
   float acc = base_margin;
-  const float* x = s_x + threadIdx.x * xs;
   for (int tile = 0; tile < n_tiles; ++tile) {
     const int t_begin = tile_ptr[tile], t_end = tile_ptr[tile + 1];
-    const int nbase = tree_ptr[t_begin];
-    const int nn = tree_ptr[t_end] - nbase;
-    __syncthreads();
-    for (int i = threadIdx.x; i < nn; i += blockDim.x) s_nodes[i] = nodes[nbase + i];
-    __syncthreads();
-    if (row < n) walk_trees<W>(s_nodes, tree_ptr, nbase, t_begin, t_end, x, [&](int, float v) { acc += v; });
+    const int nbase = fb.stage_tile(nodes, tree_ptr, t_begin, t_end);
+    if (fb.row < n)
+      walk_trees<W>(fb.s_nodes, tree_ptr, nbase, t_begin, t_end, fb.x(), [&](int, float v, uint32_t) { acc += v; });
   }
-  if (row < n) {
-    if (out_margin) out_margin[row] = acc;
-    if (out_prob) out_prob[row] = 1.0f / (1.0f + expf(-acc));
+  if (fb.row < n) {
+    if (out_margin) out_margin[fb.row] = acc;
+    if (out_prob) out_prob[fb.row] = 1.0f / (1.0f + expf(-acc));
   }
 }
 
@@ -74,21 +53,17 @@ COBALT_API int cobalt_predict(const float* X, int64_t n, int F, int64_t ldx, con
                               const int32_t* tile_ptr, int n_tiles, int tile_cap, float base_margin,
                               float* out_margin, float* out_prob, hipStream_t stream) {
   if (n <= 0) return 0;
-  if (tile_cap < 1 || tile_cap > kMaxTileNodes) return -2;
   const int block = 256;
-  const size_t lds = (size_t)tile_cap * sizeof(uint2) + (size_t)block * (F | 1) * sizeof(float);
-  if (lds > 160 * 1024) return -3;
+  if (const int rc = forest_limits(tile_cap, F, block)) return rc;
+  const size_t lds = forest_lds_bytes(tile_cap, F, block);
   static const int walk = [] {
     const int w = cobalt::knob_int(cobalt::Knob::PredWalk, kWalk);
     return (w == 2 || w == 8) ? w : kWalk;
   }();
   const void* fn = walk == 2 ? (const void*)k_predict<2> : walk == 8 ? (const void*)k_predict<8>
                                                                        : (const void*)k_predict<kWalk>;
-  static size_t attr_set = 64 * 1024;
-  if (lds > attr_set) {
-    CK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = lds;
-  }
+  static size_t attr_set = kDefaultMaxLds;
+  CK(raise_dynamic_lds(fn, lds, attr_set));
   const int grid = ceil_div(n, block);
   const uint2* nd = static_cast<const uint2*>(nodes);
   if (walk == 2)
@@ -114,27 +89,13 @@ __global__ __launch_bounds__(256) void k_predict_leaves(const float* __restrict_
                                                         const int32_t* __restrict__ tree_ptr,
                                                         const int32_t* __restrict__ tile_ptr,
                                                         float* __restrict__ leaves, int tile_cap) {
-  extern __shared__ unsigned char smem[];
-  uint2* s_nodes = reinterpret_cast<uint2*>(smem);
-  float* s_x = reinterpret_cast<float*>(smem + (size_t)tile_cap * sizeof(uint2));
-  const int xs = F | 1;
-  const int64_t row0 = (int64_t)blockIdx.x * blockDim.x;
-  const int64_t row = row0 + threadIdx.x;
-  const int nrows = (int)min((int64_t)blockDim.x, n - row0);
+  const ForestBlock<> fb(tile_cap, F, n);
   const int tile = blockIdx.y;
   const int t_begin = tile_ptr[tile], t_end = tile_ptr[tile + 1];
-  const int nbase = tree_ptr[t_begin];
-  const int nn = tree_ptr[t_end] - nbase;
-  for (int e = threadIdx.x; e < nrows * F; e += blockDim.x) {
-    const int r = e / F, f = e - r * F;
-    s_x[r * xs + f] = X[(row0 + r) * ldx + f];
-  }
-  for (int i = threadIdx.x; i < nn; i += blockDim.x) s_nodes[i] = nodes[nbase + i];
-  __syncthreads();
-  if (row >= n) return;
-  const float* x = s_x + threadIdx.x * xs;
-  walk_trees(s_nodes, tree_ptr, nbase, t_begin, t_end, x,
-             [&](int t, float v) { leaves[(int64_t)t * n + row] = v; });
+  const int nbase = fb.stage_rows_and_tile(X, F, ldx, nodes, tree_ptr, t_begin, t_end);
+  if (fb.row >= n) return;
+  walk_trees(fb.s_nodes, tree_ptr, nbase, t_begin, t_end, fb.x(),
+             [&](int t, float v, uint32_t) { leaves[(int64_t)t * n + fb.row] = v; });
 }
 
 __global__ void k_sum_leaves(const float* __restrict__ leaves, int64_t n, int T, float base_margin,
@@ -155,15 +116,11 @@ COBALT_API int cobalt_predict_small(const float* X, int64_t n, int F, int64_t ld
                                     int n_trees, float base_margin, float* leaves, float* out_margin,
                                     float* out_prob, hipStream_t stream) {
   if (n <= 0) return 0;
-  if (tile_cap < 1 || tile_cap > kMaxTileNodes) return -2;
   const int block = 256;
-  const size_t lds = (size_t)tile_cap * sizeof(uint2) + (size_t)block * (F | 1) * sizeof(float);
-  if (lds > 160 * 1024) return -3;
-  static size_t attr_set = 64 * 1024;
-  if (lds > attr_set) {
-    CK(hipFuncSetAttribute((const void*)k_predict_leaves, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = lds;
-  }
+  if (const int rc = forest_limits(tile_cap, F, block)) return rc;
+  const size_t lds = forest_lds_bytes(tile_cap, F, block);
+  static size_t attr_set = kDefaultMaxLds;
+  CK(raise_dynamic_lds((const void*)k_predict_leaves, lds, attr_set));
   hipLaunchKernelGGL(k_predict_leaves, dim3(ceil_div(n, block), n_tiles), dim3(block), lds, stream, X, n, F, ldx,
                      static_cast<const uint2*>(nodes), tree_ptr, tile_ptr, leaves, tile_cap);
   CK_LAUNCH();

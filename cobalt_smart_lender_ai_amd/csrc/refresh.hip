@@ -1,81 +1,42 @@
 // Leaf indices of a tree ensemble (XGBoost's pred_leaf) and the refresh of a model's node statistics and
 // leaf values on new labelled rows (XGBoost's process_type="update", updater="refresh") for gfx950.
 //
-// Same packed forest as the predictor (ops/predict_ops.py pack_forest): BFS-numbered trees, 8-byte nodes
-//   uint32 meta = left_child(16 bits, 0xFFFF = leaf) | feature(15 bits) << 16 | default_left << 31
-//   float  val  = split threshold (x < val goes left) or leaf value
-// grouped into tiles that are staged in LDS.
+// The packed forest, its tiles in LDS and the walk are those of the predictor: forest_walk.h.
 //
-// k_leaf_index     one thread per row (features in LDS with an odd stride, kLeafWalk independent chains per
-//                  thread, as k_predict); the walk keeps the node's index inside its tree and writes it at the
-//                  leaf, tree-major: idx[tree - t0][row] uint16 (a packed tree has at most 65535 nodes).
+// k_leaf_index     one thread per row (ForestBlock, walk_trees, as k_predict); walk_trees reports the leaf's
+//                  index inside its tree and it is written tree-major: idx[tree - t0][row] uint16 (a packed
+//                  tree has at most 65535 nodes).
 // k_refresh_accum  one launch per tree, grid-stride over the rows: the margin takes the previous tree's new
 //                  leaf value (looked up through that tree's index row), the row's gradient pair is computed
-//                  in fp64 and quantised exactly as the trainer does for this tree (models/gbdt_host.py
-//                  gradients_host with subsample = 1, row key = row index), and (gq, hq) is added to the
+//                  in fp64 and quantised by the trainer's own quantiser for this tree (gbdt_math.h
+//                  quantize_gh with subsample = 1, row key = row index), and (gq, hq) is added to the
 //                  row's leaf cell of a per-block LDS table of int64 pairs; the table's non-zero cells go to
 //                  global memory with 64-bit integer atomics. Integer sums: no order of additions changes them.
 // k_refresh_finalize  one block per tree: every leaf adds its sums to its ancestors (parents recovered from
 //                  the child fields; LDS integer atomics, so the internal sums are the exact sums of their
 //                  two children whatever the order), then weight, cover and gain of every node in fp64 by the
-//                  host trainer's expressions, the loss change of the internal nodes, and the tree's new leaf
+//                  trainer's expressions (gbdt_math.h), the loss change of the internal nodes, and the tree's new leaf
 //                  values for the next tree's accumulate pass.
 // k_refresh_apply  adds a tree's leaf values to the margins (after the last tree of a group of trees).
 // There are no floating-point atomics: the same input gives the same bits on every run and for every grouping
 // of the trees.
 #include "common.h"
+#include "forest_walk.h"
+#include "gbdt_math.h"
 #include <algorithm>
 
 using namespace cobalt;
 
 namespace {
-constexpr int kMaxTileNodes = 8192;  // as predict.hip
 constexpr int kLeafBlock = 256;
-constexpr int kLeafWalk = 4;         // trees walked at once by one thread (forest_walk.h kWalk)
 constexpr int kAccBlock = 256;
 constexpr int kAccRowsPerThread = 8; // rows a thread takes before the grid is widened
 constexpr int kAccMaxGrid = 2048;    // 8 blocks on each of the 256 CUs
 constexpr int kFinBlock = 256;
-constexpr size_t kMaxLds = 160 * 1024;
 constexpr uint32_t kLeaf = 0xFFFFu;
 
-// The trainer's fixed-point quantiser (csrc/gbdt.hip quantize_gh, models/gbdt_host.py gradients_host):
-// q = floor(x * scale + u) with u ~ U[0, 1) from the high / low half of one splitmix64 draw per (tree, row).
-constexpr int64_t kGClip = (1 << 17) - 1, kHClip = 1 << 17;
-constexpr int64_t kGClipW = (1 << 25) - 1, kHClipW = 1 << 25;
-constexpr uint64_t kDitherSalt = 0xD1B54A32D192ED03ull;
-
-inline uint64_t dither_key(uint64_t seed, int tree) {
-  const uint64_t tree_key = splitmix64(seed ^ (0xA5A5A5A5ull + (uint64_t)tree * 0x632BE59BD9B4E019ull));
-  return splitmix64(tree_key ^ kDitherSalt);
-}
-
-__device__ __forceinline__ void quantize(double g, double h, double gscale, double hscale, uint64_t dkey,
-                                         int64_t row, bool wide, int64_t& gq, int64_t& hq) {
-  const uint64_t r = splitmix64(dkey ^ (uint64_t)row);
-  const double ug = (double)(uint32_t)(r >> 32) * (1.0 / 4294967296.0);
-  const double uh = (double)(uint32_t)r * (1.0 / 4294967296.0);
-  gq = (int64_t)floor(g * gscale + ug);
-  hq = (int64_t)floor(h * hscale + uh);
-  const int64_t gc = wide ? kGClipW : kGClip, hc = wide ? kHClipW : kHClip;
-  gq = gq > gc ? gc : (gq < -gc ? -gc : gq);
-  hq = hq > hc ? hc : (hq < 0 ? 0 : hq);
-}
-
-// models/gbdt_host.py _thresh_l1 / _calc_weight / _calc_gain
-__device__ __forceinline__ double thresh_l1(double g, double alpha) {
-  if (alpha == 0.0) return g;
-  return g > alpha ? g - alpha : (g < -alpha ? g + alpha : 0.0);
-}
-__device__ __forceinline__ double calc_weight(double g, double h, double lambda, double alpha, double mcw) {
-  if (h < mcw || h <= 0.0) return 0.0;
-  return -thresh_l1(g, alpha) / (h + lambda);
-}
-__device__ __forceinline__ double calc_gain(double g, double h, double lambda, double alpha, double mcw) {
-  if (h < mcw) return 0.0;
-  const double t = thresh_l1(g, alpha);
-  return (t * t) / (h + lambda);
-}
+// The key of the trainer's dither draws for one tree (gbdt.hip computes it per tree on the device).
+inline uint64_t dither_key(uint64_t seed, int tree) { return splitmix64(tree_key_of(seed, tree) ^ kDitherSalt); }
 }  // namespace
 
 // Trees [t0, t1) of the forest: idx[(t - t0) * n + row] = index of the row's leaf inside tree t.
@@ -84,56 +45,16 @@ __global__ __launch_bounds__(kLeafBlock) void k_leaf_index(const float* __restri
                                                            const int32_t* __restrict__ tree_ptr,
                                                            const int32_t* __restrict__ tile_ptr, int n_tiles, int t0,
                                                            int t1, uint16_t* __restrict__ idx, int tile_cap) {
-  extern __shared__ unsigned char smem[];
-  uint2* s_nodes = reinterpret_cast<uint2*>(smem);
-  float* s_x = reinterpret_cast<float*>(smem + (size_t)tile_cap * sizeof(uint2));
-  const int xs = F | 1;  // odd stride -> conflict-free LDS reads
-  const int64_t row0 = (int64_t)blockIdx.x * kLeafBlock;
-  const int64_t row = row0 + threadIdx.x;
-  const int nrows = (int)min((int64_t)kLeafBlock, n - row0);
-  for (int e = threadIdx.x; e < nrows * F; e += kLeafBlock) {
-    const int r = e / F, f = e - r * F;
-    s_x[r * xs + f] = X[(row0 + r) * ldx + f];
-  }
-  const float* x = s_x + threadIdx.x * xs;
+  const ForestBlock<kLeafBlock> fb(tile_cap, F, n);
+  fb.stage_rows<false>(X, F, ldx);
   for (int tile = 0; tile < n_tiles; ++tile) {
     // the part of the tile inside [t0, t1); the bounds are the same for every thread of the block
     const int t_begin = max(tile_ptr[tile], t0), t_end = min(tile_ptr[tile + 1], t1);
     if (t_begin >= t_end) continue;
-    const int nbase = tree_ptr[t_begin];
-    const int nn = tree_ptr[t_end] - nbase;  // <= the tile's nodes <= tile_cap
-    __syncthreads();
-    for (int i = threadIdx.x; i < nn; i += kLeafBlock) s_nodes[i] = nodes[nbase + i];
-    __syncthreads();
-    if (row >= n) continue;
-    for (int t = t_begin; t < t_end; t += kLeafWalk) {
-      uint32_t base[kLeafWalk], at[kLeafWalk];
-      uint2 nd[kLeafWalk];
-#pragma unroll
-      for (int k = 0; k < kLeafWalk; ++k) {  // past the range's end: walk tree t again, result unused
-        base[k] = (uint32_t)(tree_ptr[t + k < t_end ? t + k : t] - nbase);
-        at[k] = 0;
-        nd[k] = s_nodes[base[k]];
-      }
-      bool more = true;
-      while (more) {
-        more = false;
-#pragma unroll
-        for (int k = 0; k < kLeafWalk; ++k) {
-          if ((nd[k].x & kLeaf) != kLeaf) {
-            const int f = (nd[k].x >> 16) & 0x7FFF;
-            const float v = x[f];
-            const bool left = (v != v) ? ((nd[k].x >> 31) != 0) : (v < __uint_as_float(nd[k].y));
-            at[k] = (nd[k].x & kLeaf) + (left ? 0u : 1u);
-            nd[k] = s_nodes[base[k] + at[k]];
-            more = true;
-          }
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < kLeafWalk; ++k)
-        if (t + k < t_end) idx[(int64_t)(t + k - t0) * n + row] = (uint16_t)at[k];
-    }
+    const int nbase = fb.stage_tile(nodes, tree_ptr, t_begin, t_end);
+    if (fb.row >= n) continue;
+    walk_trees(fb.s_nodes, tree_ptr, nbase, t_begin, t_end, fb.x(),
+               [&](int t, float, uint32_t at) { idx[(int64_t)(t - t0) * n + fb.row] = (uint16_t)at; });
   }
 }
 
@@ -158,7 +79,7 @@ __global__ __launch_bounds__(kAccBlock) void k_refresh_accum(
     const double g = (p - yd) * wd;
     const double h = fmax(p * (1.0 - p), 1e-16) * wd;
     int64_t gq, hq;
-    quantize(g, h, gscale, hscale, dkey, i, wide != 0, gq, hq);
+    quantize_gh(g, h, gscale, hscale, dkey, i, gq, hq, wide != 0);
     const int c = idx_cur[i];
     if (c < n_nodes) {  // (always: the index was written by k_leaf_index for this tree)
       if (gq != 0) atomicAdd(&s_tab[2 * c], (unsigned long long)gq);
@@ -231,14 +152,10 @@ __global__ __launch_bounds__(kAccBlock) void k_refresh_apply(float* __restrict__
 static int leaf_index_launch(const float* X, int64_t n, int F, int64_t ldx, const uint2* nodes,
                              const int32_t* tree_ptr, const int32_t* tile_ptr, int n_tiles, int tile_cap, int t0,
                              int t1, uint16_t* idx, hipStream_t stream) {
-  if (tile_cap < 1 || tile_cap > kMaxTileNodes) return -2;
-  const size_t lds = (size_t)tile_cap * sizeof(uint2) + (size_t)kLeafBlock * (F | 1) * sizeof(float);
-  if (lds > kMaxLds) return -3;
-  static size_t attr_set = 64 * 1024;
-  if (lds > attr_set) {
-    CK(hipFuncSetAttribute((const void*)k_leaf_index, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = lds;
-  }
+  if (const int rc = forest_limits(tile_cap, F, kLeafBlock)) return rc;
+  const size_t lds = forest_lds_bytes(tile_cap, F, kLeafBlock);
+  static size_t attr_set = kDefaultMaxLds;
+  CK(raise_dynamic_lds((const void*)k_leaf_index, lds, attr_set));
   hipLaunchKernelGGL(k_leaf_index, dim3(ceil_div(n, kLeafBlock)), dim3(kLeafBlock), lds, stream, X, n, F, ldx, nodes,
                      tree_ptr, tile_ptr, n_tiles, t0, t1, idx, tile_cap);
   CK_LAUNCH();
@@ -282,8 +199,7 @@ COBALT_API int cobalt_refresh(const float* X, int64_t n, int F, int64_t ldx, con
   if (group_trees < 1 || (grad_bits != 17 && grad_bits != 25) || !(gscale > 0.0) || !(hscale > 0.0) ||
       tree_ptr_host == nullptr || tree_ptr_host[0] != 0)
     return -6;
-  if (tile_cap < 1 || tile_cap > kMaxTileNodes) return -2;
-  if ((size_t)tile_cap * sizeof(uint2) + (size_t)kLeafBlock * (F | 1) * sizeof(float) > kMaxLds) return -3;
+  if (const int rc = forest_limits(tile_cap, F, kLeafBlock)) return rc;
   int biggest = 0;
   for (int t = 0; t < n_trees; ++t) {
     const int nn = tree_ptr_host[t + 1] - tree_ptr_host[t];
@@ -292,16 +208,9 @@ COBALT_API int cobalt_refresh(const float* X, int64_t n, int F, int64_t ldx, con
   }
   if (biggest > cobalt_refresh_max_nodes()) return -5;
   const size_t lds_acc = (size_t)biggest * 16, lds_fin = (size_t)biggest * 26;
-  static size_t acc_set = 64 * 1024, fin_set = 64 * 1024;
-  if (lds_acc > acc_set) {
-    CK(hipFuncSetAttribute((const void*)k_refresh_accum, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_acc));
-    acc_set = lds_acc;
-  }
-  if (lds_fin > fin_set) {
-    CK(hipFuncSetAttribute((const void*)k_refresh_finalize, hipFuncAttributeMaxDynamicSharedMemorySize,
-                           (int)lds_fin));
-    fin_set = lds_fin;
-  }
+  static size_t acc_set = kDefaultMaxLds, fin_set = kDefaultMaxLds;
+  CK(raise_dynamic_lds((const void*)k_refresh_accum, lds_acc, acc_set));
+  CK(raise_dynamic_lds((const void*)k_refresh_finalize, lds_fin, fin_set));
   const int64_t M = tree_ptr_host[n_trees];
   const uint2* nd = static_cast<const uint2*>(nodes);
   unsigned long long* tab = reinterpret_cast<unsigned long long*>(sums);
