@@ -461,7 +461,7 @@ __global__ __launch_bounds__(1024) void k_sk_exact(const int64_t* __restrict__ c
                                                    const int32_t* __restrict__ ndist, const float* __restrict__ dval,
                                                    const int64_t* __restrict__ maxb, float* __restrict__ cuts_ex,
                                                    int64_t* __restrict__ nd) {
-  constexpr int kPer = (kSkBuckets + 1023) / 1024;  // buckets per thread (8)
+  constexpr int kPer = (kSkBuckets + 1023) / 1024;  // buckets per thread (9)
   __shared__ int64_t s_tot[1024 / kWave];
   __shared__ int s_bad;
   const int f = blockIdx.x, t = threadIdx.x;
