@@ -1,5 +1,5 @@
 // "A block scores its rows against tiles of the packed forest": the one home of what the forest kernels
-// share (predict.hip, evalcurve.hip, pdp.hip, permimp.hip, refresh.hip k_leaf_index). Forest layout
+// share (predict.hip, evalcurve.hip, pdp.hip, permimp.hip, ale.hip, refresh.hip k_leaf_index). Forest layout
 // (ops/predict_ops.py pack_forest): BFS-numbered trees, 8-byte nodes
 //   uint32 meta = left_child(16 bits, 0xFFFF = leaf) | feature(15 bits) << 16 | default_left << 31
 //   float  val  = split threshold (x < val goes left) or leaf value

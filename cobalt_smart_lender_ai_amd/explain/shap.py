@@ -264,6 +264,79 @@ def pd_plot(result: dict, ice: bool = True, max_ice: int = 200, centered: bool =
     return fig
 
 
+# -------------------------------------------------------------------- accumulated local effects
+def accumulated_local_effects(model, X, features=None, **kw):
+    """Accumulated local effects (:meth:`Booster.accumulated_local_effects`) of a ``GBDTClassifier``, a
+    ``Booster`` or a :class:`TreeExplainer`: the effect of a feature (or the interaction of a pair) measured
+    only where the rows are, which partial dependence is not for correlated features. A classifier scores the
+    trees ``predict_proba`` scores (the first ``best_iteration + 1`` of an early-stopped fit, or
+    ``iteration_range=(0, n)``), on its device, and a DataFrame's columns are reordered by feature name."""
+    if isinstance(model, TreeExplainer):
+        kw.setdefault("device", model.device)
+        return model.booster.accumulated_local_effects(X, features, **kw)
+    if isinstance(model, Booster):
+        return model.accumulated_local_effects(X, features, **kw)
+    if hasattr(model, "get_booster") and hasattr(model, "_n_trees"):
+        if "n_trees" in kw and "iteration_range" in kw:
+            raise ValueError("pass n_trees or iteration_range, not both")
+        if "n_trees" not in kw:
+            kw["n_trees"] = model._n_trees(kw.pop("iteration_range", None))
+        kw.setdefault("device", model.device)
+        return model.get_booster().accumulated_local_effects(model._matrix(X), features, **kw)
+    raise TypeError("expected a GBDTClassifier, a Booster or a TreeExplainer")
+
+
+def _ale_axes(ax, r: dict) -> None:
+    """One :func:`accumulated_local_effects` result on ``ax``."""
+    names = list(r["feature_names"])
+    edges = [np.asarray(z, np.float64) for z in r["edges"]]
+    ale = np.asarray(r["ale"], np.float64)
+    wgt = np.asarray(r["interval_weight"], np.float64)
+    if len(edges) == 2:
+        if ale.shape[0] >= 2 and ale.shape[1] >= 2:
+            cs = ax.contourf(edges[0], edges[1], ale.T, levels=12, cmap="RdBu_r")
+        else:
+            cs = ax.imshow(ale.T, origin="lower", aspect="auto", cmap="RdBu_r")
+        ax.figure.colorbar(cs, ax=ax, label="ALE (second order)")
+        ax.set_xlabel(names[0])
+        ax.set_ylabel(names[1])
+        return
+    z = edges[0] if len(edges[0]) == len(ale) else np.zeros(len(ale))
+    ax.plot(z, ale, color="#08519c", lw=2.0, marker="o" if len(ale) < 3 else None)
+    ax.axhline(0, color="grey", lw=0.8)
+    if wgt.size and wgt.sum() > 0:  # the rug: one tick per interval at its midpoint, as tall as its share of weight
+        mid = (z[:-1] + z[1:]) / 2
+        lo, hi = ax.get_ylim()
+        ax.vlines(mid, lo, lo + 0.12 * (hi - lo) * wgt / wgt.max(), color="#6b6b6b", lw=1.2)
+        ax.set_ylim(lo, hi)
+    ax.set_xlabel(names[0])
+    ax.set_ylabel("ALE")
+
+
+def ale_plot(result, max_cols: int = 4):
+    """Draw an :func:`accumulated_local_effects` result. One feature: the curve on its edges over a rug of the
+    interval weights (where the rows are). A pair: a filled contour of the second-order effect. A list: one
+    panel per result."""
+    plt = _plt()
+    if isinstance(result, dict):
+        fig, ax = plt.subplots(figsize=(8, 5) if len(result["edges"]) == 1 else (7, 5.5))
+        _ale_axes(ax, result)
+        fig.tight_layout()
+        return fig
+    results = list(result)
+    if not results:
+        raise ValueError("nothing to draw")
+    cols = min(max_cols, len(results))
+    rows = (len(results) + cols - 1) // cols
+    fig, axes = plt.subplots(rows, cols, figsize=(4.2 * cols, 3.4 * rows), squeeze=False)
+    for ax, r in zip(axes.ravel(), results):
+        _ale_axes(ax, r)
+    for ax in axes.ravel()[len(results):]:
+        ax.set_visible(False)
+    fig.tight_layout()
+    return fig
+
+
 # ----------------------------------------------------------------------- permutation importance
 def permutation_importance(model, X, y, features=None, **kw) -> dict:
     """Permutation feature importance (:meth:`Booster.permutation_importance`) of a ``GBDTClassifier``, a

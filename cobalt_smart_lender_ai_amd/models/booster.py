@@ -475,6 +475,129 @@ class Booster:
                 "baseline_score": float(base[metric]), "scores": sc, "features": feats,
                 "feature_names": [names[f] for f in feats], "metric": metric, "n_repeats": int(sc.shape[1])}
 
+    def accumulated_local_effects(self, X, features=None, *, grid=None, grid_resolution: int = 20,
+                                  response: str = "probability", sample_weight=None, centered: bool = True,
+                                  n_trees: int | None = None, device: str | None = None):
+        """Accumulated local effects (ALE, Apley & Zhu 2020) of one feature or a pair: what the model does as the
+        feature moves, measured only where the rows are. Partial dependence scores every row at every grid
+        value, which for correlated features is mostly combinations that never occur; ALE moves each row only
+        across the interval of ``edges`` it already lies in (everything else as in ``X``, which is not
+        modified), averages the prediction differences per interval, accumulates the averages and centres them
+        (:func:`ale_host`, :func:`ale_curve`: the definition).
+
+        ``features``: None = every model feature, one curve each (a list of results); an index or a name = one
+        curve; a tuple of two = the second-order effect of the pair on the lattice of both edge vectors (the
+        pure interaction: both main effects are subtracted; identically 0 when no tree uses both); a list of
+        indices, names or pairs = a list of results. ``grid``: explicit edges (one increasing finite vector, a
+        pair of vectors for a pair, a list of those -- or None -- for a list); values outside them are clamped
+        into the end intervals. By default :func:`ale_edges` builds ``grid_resolution`` intervals of about equal
+        row counts from the column's quantiles. ``response``: "probability" (differences of per-row
+        probabilities) or "margin" (log-odds). ``sample_weight`` weights the interval means and the centring.
+        ``centered=False`` returns the accumulated curve that starts at 0. ``n_trees``: score that prefix of the
+        forest.
+
+        Each result is ``{"feature_names": [...], "edges": [float32 vector, ...], "ale": float64 [K + 1] or
+        [K1 + 1, K2 + 1] (on the edges), "interval_effect": float64 [K] or [K1, K2] (mean effect per interval
+        / cell), "interval_weight": the same shape (sum of weights), "n_missing": rows left out for a NaN in the
+        feature(s)}``. An interval without rows has effect 0 and carries the curve forward; in 2-D an empty
+        cell is 0 too, where R's ALEPlot fills it from the nearest non-empty cell. A column with fewer than
+        two distinct values gives the single point 0.0. On a GPU every feature (pair) is one job of
+        ``csrc/ale.hip``: corner margins have the bits of ``predict_margin`` on the substituted rows and the
+        interval sums are reduced in a fixed order (same input, same bits)."""
+        from ..ops import predict_ops
+
+        if response not in ("probability", "margin"):
+            raise ValueError(f"response must be 'probability' or 'margin', got {response!r}")
+        single = False
+        if features is None:
+            items = list(range(self.num_feature))
+        elif isinstance(features, (list, np.ndarray)):
+            items = list(features)
+        else:  # one index or name, or one pair (a tuple)
+            items, single = [features], True
+        jobs: list[tuple[int, ...]] = []
+        for it in items:
+            if isinstance(it, (tuple, list)):
+                if len(it) != 2:
+                    raise ValueError(f"a feature pair has two entries, got {it!r}")
+                pair = tuple(self._feature_index(f) for f in it)
+                if pair[0] == pair[1]:
+                    raise ValueError(f"the two features must differ, got {it!r}")
+                jobs.append(pair)
+            else:
+                jobs.append((self._feature_index(it),))
+        names = self.feature_names or [f"f{i}" for i in range(self.num_feature)]
+        if hasattr(X, "columns") and self.feature_names:
+            X = X[self.feature_names]
+        if hasattr(X, "to_numpy"):
+            X = X.to_numpy(dtype=np.float32, na_value=np.nan)
+        if not hasattr(X, "shape") or len(X.shape) != 2:
+            X = np.asarray(X, dtype=np.float32)
+            if X.ndim != 2:
+                raise ValueError(f"X must be [rows, features], got shape {X.shape}")
+        N = int(X.shape[0])
+        if N == 0 or X.shape[1] < self.num_feature:
+            raise ValueError(f"X has shape {tuple(X.shape)}, model needs [rows >= 1, >= {self.num_feature}]")
+        w = None
+        if sample_weight is not None:
+            w = np.asarray(sample_weight.detach().cpu().numpy() if hasattr(sample_weight, "detach")
+                           else sample_weight, dtype=np.float32).reshape(-1)
+            if w.shape[0] != N:
+                raise ValueError(f"X has {N} rows, sample_weight has {w.shape[0]}")
+            if not bool((w >= 0).all()) or not float(np.sum(w, dtype=np.float64)) > 0:  # (NaN fails too)
+                raise ValueError("sample_weight must be non-negative with a positive sum")
+        if grid is None:
+            grids = [None] * len(jobs)
+        elif single:
+            grids = [grid]
+        else:
+            grids = list(grid)
+            if len(grids) != len(jobs):
+                raise ValueError(f"{len(jobs)} features need {len(jobs)} grids, got {len(grids)}")
+        if int(grid_resolution) < 1:
+            raise ValueError(f"grid_resolution must be at least 1, got {grid_resolution}")
+        cols: dict[int, np.ndarray] = {}
+
+        def column(f: int) -> np.ndarray:
+            if f not in cols:
+                c = X[:, f]
+                cols[f] = np.asarray(c.detach().cpu().numpy() if hasattr(c, "detach") else c, dtype=np.float32)
+            return cols[f]
+
+        edges: list[list[np.ndarray]] = []
+        for feats, g in zip(jobs, grids):
+            if g is None:
+                edges.append([ale_edges(column(f), int(grid_resolution)) for f in feats])
+            else:
+                given = [g] if len(feats) == 1 else list(g)
+                if len(given) != len(feats):
+                    raise ValueError(f"{len(feats)} features need {len(feats)} edge vectors, got {len(given)}")
+                edges.append([check_ale_edges(z) for z in given])
+        live = [i for i, ez in enumerate(edges) if all(len(z) >= 2 for z in ez)]
+        sums = predict_ops.accumulated_local_effects(self, X, [jobs[i] for i in live], [edges[i] for i in live],
+                                                     n_trees=n_trees, weights=w, device=device) if live else []
+        by_job = dict(zip(live, sums))
+        out = []
+        for i, (feats, ez) in enumerate(zip(jobs, edges)):
+            res: dict[str, Any] = {"feature_names": [names[f] for f in feats], "edges": ez}
+            if i in by_job:
+                s = by_job[i]
+                S = s["sum_prob"] if response == "probability" else s["sum_margin"]
+                res["ale"], res["interval_effect"] = ale_curve(S, s["weight"], centered)
+                res["interval_weight"] = np.asarray(s["weight"], np.float64)
+                res["n_missing"] = int(s["n_missing"])
+            else:  # a constant (or empty) column: no interval, the single point 0.0
+                shape = tuple(max(len(z) - 1, 0) for z in ez)
+                res["ale"] = np.zeros(tuple(max(len(z), 1) for z in ez), np.float64)
+                res["interval_effect"] = np.zeros(shape, np.float64)
+                res["interval_weight"] = np.zeros(shape, np.float64)
+                miss = np.zeros(N, dtype=bool)
+                for f in feats:
+                    miss |= np.isnan(column(f))
+                res["n_missing"] = int(miss.sum())
+            out.append(res)
+        return out[0] if single else out
+
     def expected_value(self) -> float:
         """TreeExplainer ``expected_value``: base margin + cover-weighted mean leaf value per tree."""
         tot = 0.0
@@ -1177,6 +1300,148 @@ def pd_grid_axis(col: np.ndarray, grid_resolution: int, percentiles: tuple[float
         return uniq.astype(np.float32)
     lo, hi = (np.quantile(vals, q) for q in percentiles)
     return np.linspace(lo, hi, grid_resolution).astype(np.float32)
+
+
+# -------------------------------------------------------------------- accumulated local effects
+def check_ale_edges(z) -> np.ndarray:
+    """Interval edges as a float32 vector: finite, strictly increasing, at least two. ``ValueError`` otherwise."""
+    z = np.asarray(z.detach().cpu().numpy() if hasattr(z, "detach") else z)
+    if z.ndim != 1 or z.shape[0] < 2:
+        raise ValueError(f"ALE edges must be a vector of at least 2 values, got shape {z.shape}")
+    z = np.ascontiguousarray(z, dtype=np.float32)
+    if not bool(np.isfinite(z).all()) or not bool((z[1:] > z[:-1]).all()):
+        raise ValueError("ALE edges must be finite and strictly increasing (as float32)")
+    return z
+
+
+def ale_edges(col: np.ndarray, grid_resolution: int = 20) -> np.ndarray:
+    """The default interval edges of a column for ALE, float32 and strictly increasing, from its finite values
+    (NaN rows are left out of ALE, +-inf rows fall in the end intervals): the distinct values when there are
+    at most ``grid_resolution + 1`` of them, else the distinct float32 values of ``np.quantile(vals,
+    linspace(0, 1, grid_resolution + 1))`` (intervals of about equal row counts). Fewer than two values come
+    back for a constant or empty column: there is no interval then."""
+    if int(grid_resolution) < 1:
+        raise ValueError(f"grid_resolution must be at least 1, got {grid_resolution}")
+    col = np.asarray(col, dtype=np.float32).reshape(-1)
+    vals = col[np.isfinite(col)]
+    uniq = np.unique(vals)
+    if uniq.shape[0] <= int(grid_resolution) + 1:
+        return uniq.astype(np.float32)
+    q = np.quantile(vals.astype(np.float64), np.linspace(0.0, 1.0, int(grid_resolution) + 1))
+    return np.unique(q.astype(np.float32))
+
+
+def ale_interval_host(z: np.ndarray, x: np.ndarray) -> np.ndarray:
+    """The interval ``k`` in [1, K] of every value of ``x`` among the edges ``z[0..K]``: ``clamp(searchsorted(z,
+    x, "left"), 1, K)``, so ``z[k-1] < x <= z[k]``; values at or below ``z[0]`` (``-inf``) fall in interval 1,
+    values beyond ``z[K]`` (``+inf``) in interval K. NaN gives 1 (the caller leaves such rows out)."""
+    z = np.asarray(z, dtype=np.float32)
+    x = np.asarray(x, dtype=np.float32)
+    k = np.searchsorted(z, np.where(np.isnan(x), -np.inf, x).astype(np.float32), side="left")
+    return np.clip(k, 1, len(z) - 1).astype(np.int64)
+
+
+def ale_host(b: Booster, X: np.ndarray, feats: Sequence[int], edges: Sequence[np.ndarray],
+             n_trees: int | None = None, weights: np.ndarray | None = None) -> dict[str, Any]:
+    """The definition of the accumulated-local-effects sums (CPU path and oracle of ``csrc/ale.hip``) for one
+    feature or a pair. A row lies in interval ``k`` of ``edges[0]`` (:func:`ale_interval_host`; with two
+    features in cell ``(k, l)``) and is scored with :func:`predict_margin_host` at the corners: corner
+    ``c = i1 + 2 i2`` has ``x[feats[0]] = edges[0][k - 1 + i1]`` (and ``x[feats[1]] = edges[1][l - 1 + i2]``),
+    everything else as in ``X``. The row's effect is ``hi - lo`` (1-D) or ``(c3 - c2) - (c1 - c0)`` (2-D), in
+    margin units from the float32 corner margins widened to float64 and in probability units from ``1 / (1 +
+    exp(-m))`` per corner in float64. Rows with NaN in a feature of the job are left out and counted.
+
+    Returns ``{"corners": float32 [C, N], "cell": int64 [N] (k - 1, or (k - 1) * K2 + (l - 1); -1 = left
+    out), "sum_margin", "sum_prob", "weight": float64 [K1] or [K1, K2] (sum w effect, sum w per interval,
+    ``math.fsum``), "n_missing"}``. ``X`` is not modified."""
+    X = np.asarray(X, dtype=np.float32)
+    N = X.shape[0]
+    feats = [int(f) for f in feats]
+    if len(feats) not in (1, 2) or len(edges) != len(feats):
+        raise ValueError(f"ALE takes one or two features with one edge vector each, got {len(feats)} and {len(edges)}")
+    for f in feats:
+        if not 0 <= f < b.num_feature:
+            raise ValueError(f"feature index {f} outside [0, {b.num_feature})")
+    if len(feats) == 2 and feats[0] == feats[1]:
+        raise ValueError(f"the two features must differ, got {feats}")
+    edges = [check_ale_edges(z) for z in edges]
+    Ks = [len(z) - 1 for z in edges]
+    wd = np.ones(N, dtype=np.float64) if weights is None else np.asarray(weights, dtype=np.float32).astype(np.float64)
+    if wd.shape[0] != N:
+        raise ValueError(f"X has {N} rows, weights has {wd.shape[0]}")
+    miss = np.zeros(N, dtype=bool)
+    ks = []
+    for f, z in zip(feats, edges):
+        miss |= np.isnan(X[:, f])
+        ks.append(ale_interval_host(z, X[:, f]))
+    C = 1 << len(feats)
+    corners = np.empty((C, N), dtype=np.float32)
+    Xs = X.copy()
+    for c in range(C):
+        for a, (f, z) in enumerate(zip(feats, edges)):
+            Xs[:, f] = z[ks[a] - 1 + ((c >> a) & 1)]
+        corners[c] = predict_margin_host(b, Xs, n_trees)
+    m = corners.astype(np.float64)
+    with np.errstate(over="ignore"):
+        p = 1.0 / (1.0 + np.exp(-m))
+    if C == 2:
+        dm, dp = m[1] - m[0], p[1] - p[0]
+        cell = ks[0] - 1
+    else:
+        dm, dp = (m[3] - m[2]) - (m[1] - m[0]), (p[3] - p[2]) - (p[1] - p[0])
+        cell = (ks[0] - 1) * Ks[1] + (ks[1] - 1)
+    cell = np.where(miss, -1, cell)
+    ncell = int(np.prod(Ks))
+    sm, sp, sw = np.zeros(ncell), np.zeros(ncell), np.zeros(ncell)
+    order = np.argsort(cell, kind="stable")
+    bounds = np.searchsorted(cell[order], np.arange(ncell + 1))
+    for c in range(ncell):
+        idx = order[bounds[c]:bounds[c + 1]]
+        if idx.size:
+            sm[c] = math.fsum(wd[idx] * dm[idx])
+            sp[c] = math.fsum(wd[idx] * dp[idx])
+            sw[c] = math.fsum(wd[idx])
+    shape = tuple(Ks)
+    return {"corners": corners, "cell": cell, "sum_margin": sm.reshape(shape), "sum_prob": sp.reshape(shape),
+            "weight": sw.reshape(shape), "n_missing": int(miss.sum())}
+
+
+def ale_curve(S: np.ndarray, W: np.ndarray, centered: bool = True) -> tuple[np.ndarray, np.ndarray]:
+    """``(ale, interval_effect)`` from the per-interval sums ``S = sum w effect`` and ``W = sum w`` (float64 [K]
+    or [K1, K2]); shared by the CPU and the GPU path.
+
+    1-D: ``e_k = S_k / W_k`` (0 for an empty interval, which carries the curve forward), ``A[0] = 0``,
+    ``A[k] = A[k-1] + e_k`` on the K + 1 edges and ``ale = A - sum_k W_k (A[k-1] + A[k]) / 2 / sum_k W_k``.
+
+    2-D (Apley & Zhu, eq. 13-16): the cell means (0 for an empty cell; ALEPlot fills empty cells from the
+    nearest non-empty one instead) are accumulated along both axes on the (K1 + 1) x (K2 + 1) lattice,
+    ``A[0, :] = A[:, 0] = 0``; the accumulated main effect of ``A`` along each axis is subtracted,
+    ``g1[k] = sum_{k' <= k} sum_l W_k'l ((A[k',l] - A[k'-1,l]) + (A[k',l-1] - A[k'-1,l-1])) / 2 / sum_l W_k'l``
+    (a row of cells without weight adds nothing) and ``g2`` likewise; then the W-weighted mean over the cells
+    of the four-corner average. What is left is the pure second-order effect.
+
+    ``centered=False`` returns ``A`` itself."""
+    S = np.asarray(S, dtype=np.float64)
+    W = np.asarray(W, dtype=np.float64)
+    e = np.divide(S, W, out=np.zeros_like(S), where=W > 0)
+    if S.ndim == 1:
+        A = np.concatenate([[0.0], np.cumsum(e)])
+        if centered and W.sum() > 0:
+            A = A - float((W * (A[:-1] + A[1:]) / 2).sum() / W.sum())
+        return A, e
+    K1, K2 = S.shape
+    A = np.zeros((K1 + 1, K2 + 1))
+    A[1:, 1:] = np.cumsum(np.cumsum(e, axis=0), axis=1)
+    if not centered or W.sum() <= 0:
+        return A, e
+    d1 = ((A[1:, 1:] - A[:-1, 1:]) + (A[1:, :-1] - A[:-1, :-1])) / 2      # [K1, K2]: along axis 1, cell (k, l)
+    d2 = ((A[1:, 1:] - A[1:, :-1]) + (A[:-1, 1:] - A[:-1, :-1])) / 2
+    w1, w2 = W.sum(axis=1), W.sum(axis=0)
+    g1 = np.concatenate([[0.0], np.cumsum(np.divide((W * d1).sum(axis=1), w1, out=np.zeros(K1), where=w1 > 0))])
+    g2 = np.concatenate([[0.0], np.cumsum(np.divide((W * d2).sum(axis=0), w2, out=np.zeros(K2), where=w2 > 0))])
+    A = A - g1[:, None] - g2[None, :]
+    four = (A[:-1, :-1] + A[:-1, 1:] + A[1:, :-1] + A[1:, 1:]) / 4
+    return A - float((W * four).sum() / W.sum()), e
 
 
 def treeshap_host(b: Booster, X: np.ndarray) -> np.ndarray:

@@ -2,8 +2,8 @@
 :class:`Booster`.
 
 GPU path: gfx950 kernels in ``csrc/predict.hip`` (forest packed once per booster and device, cached),
-``csrc/shapint.hip``, ``csrc/shapbg.hip``, ``csrc/evalcurve.hip``, ``csrc/pdp.hip``, ``csrc/permimp.hip`` and
-``csrc/refresh.hip`` (leaf indices, leaf refresh).
+``csrc/shapint.hip``, ``csrc/shapbg.hip``, ``csrc/evalcurve.hip``, ``csrc/pdp.hip``, ``csrc/permimp.hip``,
+``csrc/ale.hip`` and ``csrc/refresh.hip`` (leaf indices, leaf refresh).
 CPU path: the NumPy reference implementations in ``models/booster.py``.
 """
 from __future__ import annotations
@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..models.booster import (Booster, Tree, _refreshed_booster, check_background, check_eval_inputs,
+from ..models.booster import (Booster, Tree, _refreshed_booster, ale_host, check_ale_edges, check_background,
+                              check_eval_inputs,
                               check_model_output, check_perm_inputs, check_refresh_inputs, eval_curve_host,
                               partial_dependence_host, permutation_scores_host, predict_leaf_host,
                               predict_margin_host, refresh_host, refresh_params, refresh_row_weights,
@@ -122,6 +123,27 @@ _native.register("cobalt_perm_workspace", ctypes.c_int64, [ctypes.c_int64, ctype
 _native.register("cobalt_perm_rep_chunk", ctypes.c_int, [])
 _native.register("cobalt_perm_chunk_rows", ctypes.c_int64, [])
 PERM_REP_CHUNK = 0             # repeats per block of csrc/permimp.hip: 0 = its default, 8 or 16 (sweeps)
+
+# csrc/ale.hip: cells (X, n, F, ldx, jobs_host, jobs, J, dims, edges, n_edges, cells, stream); ale (X, n, F, ldx,
+# nodes, tree_ptr, tile_ptr, n_tiles, tile_cap, base_margin, jobs_host, jobs, J, dims, edges, n_edges, w, order,
+# seg_ptr, max_cells, rows, workspace, sums, stream)
+_native.register("cobalt_ale_cells", ctypes.c_int,
+                 [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p])
+_native.register("cobalt_ale", ctypes.c_int,
+                 [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p])
+_native.register("cobalt_ale_workspace", ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int])
+_native.register("cobalt_ale_chunk_rows", ctypes.c_int64, [])
+_native.register("cobalt_ale_max_intervals", ctypes.c_int, [])
+_native.register("cobalt_ale_max_cells", ctypes.c_int, [])
+_native.register("cobalt_ale_max_jobs", ctypes.c_int, [])
+_native.register("cobalt_ale_no_cell", ctypes.c_int, [])
+ALE_MAX_INTERVALS = 4096       # intervals per axis (csrc/ale.hip kAleMaxIntervals)
+ALE_MAX_CELLS = 1 << 16        # K1 * K2 of a pair (kAleMaxCells)
+ALE_MAX_JOBS = 65535           # features / pairs per launch (kAleMaxJobs); more are split over launches
 
 PATH_ELEM = np.dtype([("lo", "<f4"), ("hi", "<f4"), ("feat", "<i4"), ("nan_ok", "<i4"), ("zero", "<f8")])
 
@@ -719,6 +741,154 @@ def permutation_scores(b: Booster, X, y, feats, perm, *, n_trees: int | None = N
                     auc[i0 + i, r0 + r] = roc_auc(ypos, m[1 + i * (r1 - r0) + r])
         scores["auc"] = auc
     return {m: base[m] for m in metrics}, {m: scores[m] for m in metrics}
+
+
+# ------------------------------------------------------------------- accumulated local effects
+# Entries of the [jobs, N] int32 cell and order matrices of one launch series (4 + 4 bytes each: 1 GiB): more
+# jobs are split over several series, each of which stages the rows again. Results do not depend on it.
+ALE_JOB_ENTRIES = 1 << 27
+
+
+def _check_ale_args(b: Booster, jobs, edges) -> tuple[list[tuple[int, ...]], list[list[np.ndarray]]]:
+    """Jobs as tuples of one or two distinct feature indices inside the model (all of one kind), with one
+    finite, strictly increasing float32 edge vector per feature, within the kernel's limits. ``ValueError``
+    otherwise."""
+    jobs = [tuple(int(f) for f in (j if isinstance(j, (tuple, list)) else (j,))) for j in jobs]
+    if not jobs:
+        raise ValueError("no ALE job")
+    dims = len(jobs[0])
+    if len(edges) != len(jobs):
+        raise ValueError(f"{len(jobs)} jobs need {len(jobs)} edge lists, got {len(edges)}")
+    out = []
+    for feats, ez in zip(jobs, edges):
+        if len(feats) not in (1, 2) or len(feats) != dims:
+            raise ValueError(f"the jobs of one call take one feature each or two each, got {feats} next to {jobs[0]}")
+        for f in feats:
+            if not 0 <= f < b.num_feature:
+                raise ValueError(f"feature index {f} outside [0, {b.num_feature})")
+        if dims == 2 and feats[0] == feats[1]:
+            raise ValueError(f"the two features must differ, got {feats}")
+        ez = [ez] if dims == 1 and not isinstance(ez, (tuple, list)) else list(ez)
+        if len(ez) != dims:
+            raise ValueError(f"{dims} features need {dims} edge vectors, got {len(ez)}")
+        ez = [check_ale_edges(z) for z in ez]
+        if any(len(z) - 1 > ALE_MAX_INTERVALS for z in ez) or int(np.prod([len(z) - 1 for z in ez])) > ALE_MAX_CELLS:
+            raise ValueError(f"at most {ALE_MAX_INTERVALS} intervals per feature and {ALE_MAX_CELLS} cells per pair")
+        out.append(ez)
+    return jobs, out
+
+
+def accumulated_local_effects_gpu(b: Booster, X: torch.Tensor, jobs, edges, *, n_trees: int | None = None,
+                                  weights: torch.Tensor | None = None, want_rows: bool,
+                                  want_sums: bool) -> tuple[torch.Tensor | None, torch.Tensor | None]:
+    """Launch ``csrc/ale.hip`` on the current stream (no host sync). ``jobs``: tuples of one feature index each,
+    or of two each; ``edges``: per job one edge vector per feature (K + 1 increasing values = K intervals). Job
+    ``j`` scores every row at the corners of the interval / cell it lies in (``models.booster.ale_host``: corner
+    ``c = i1 + 2 i2``); ``X`` is not written. Returns ``(rows, sums)``: ``rows`` [J, C, N] float32 corner
+    margins, C = 2 or 4, with the bits of ``predict_margin`` on the substituted rows (``want_rows``); ``sums``
+    [J, max cells, 3] float64 = (sum w d_margin, sum w d_prob, sum w) per interval ``k - 1`` / cell
+    ``(k - 1) * K2 + (l - 1)`` (``want_sums``; rows with NaN in a feature of the job enter no sum). The sums
+    are grouped without atomics: the rows' cells are sorted stably per row chunk (``torch.sort``) and one block
+    per cell adds its segment in a fixed order, so the same input gives the same bits. ``X`` as for
+    :func:`predict_gpu`; ``weights``: float32 [N] on the device of ``X``. ``ValueError`` / ``RuntimeError`` (a
+    model outside the kernel's LDS limits) before anything of the walk is launched."""
+    _check_kernel_rows(b, X)
+    jobs, edges = _check_ale_args(b, jobs, edges)
+    N, F = X.shape
+    if N == 0:
+        raise ValueError("X has no rows")
+    J, dims = len(jobs), len(jobs[0])
+    if J > ALE_MAX_JOBS:
+        raise ValueError(f"{J} jobs exceed the limit of {ALE_MAX_JOBS} per call")
+    if weights is not None and (weights.dtype != torch.float32 or weights.dim() != 1 or weights.shape[0] != N
+                                or weights.device != X.device or not weights.is_contiguous()):
+        raise ValueError(f"weights must be a contiguous float32 [{N}] tensor on {X.device}")
+    desc = np.zeros((J, 6), dtype=np.int32)   # {f1, f2, off1, K1, off2, K2}
+    flat, off = [], 0
+    for j, (feats, ez) in enumerate(zip(jobs, edges)):
+        desc[j] = (feats[0], -1, off, len(ez[0]) - 1, 0, 1)
+        flat.append(ez[0])
+        off += len(ez[0])
+        if dims == 2:
+            desc[j, 1], desc[j, 4], desc[j, 5] = feats[1], off, len(ez[1]) - 1
+            flat.append(ez[1])
+            off += len(ez[1])
+    max_cells = int((desc[:, 3].astype(np.int64) * desc[:, 5]).max())
+    gf = gpu_forest(b, X.device, n_trees)
+    lib = _native.lib()
+    dev = X.device
+    jd = torch.from_numpy(desc).to(dev)
+    ed = torch.from_numpy(np.concatenate(flat)).to(dev)
+    stream = _native.stream_handle()
+    order = seg = sums = work = None
+    if want_sums:
+        cells = torch.empty((J, N), dtype=torch.int32, device=dev)
+        rc = lib.cobalt_ale_cells(X.data_ptr(), N, F, X.stride(0), desc.ctypes.data, jd.data_ptr(), J, dims,
+                                  ed.data_ptr(), off, cells.data_ptr(), stream)
+        _native.check(rc, "cobalt_ale_cells")
+        chunk = int(lib.cobalt_ale_chunk_rows())
+        starts = range(0, N, chunk)
+        order = torch.empty((J, N), dtype=torch.int32, device=dev)
+        seg = torch.empty((len(starts), J, max_cells + 1), dtype=torch.int32, device=dev)
+        bounds = torch.arange(max_cells + 1, dtype=torch.int32, device=dev).expand(J, -1).contiguous()
+        for ci, r0 in enumerate(starts):
+            srt, idx = torch.sort(cells[:, r0:r0 + chunk], dim=1, stable=True)
+            order[:, r0:r0 + chunk] = idx   # chunk-local row indices, cell by cell, ascending inside a cell
+            seg[ci] = torch.searchsorted(srt.contiguous(), bounds, out_int32=True)
+        sums = torch.zeros((J, max_cells, 3), dtype=torch.float64, device=dev)
+        if not want_rows:
+            work = torch.empty(int(lib.cobalt_ale_workspace(N, J, dims)), dtype=torch.uint8, device=dev)
+    rows = torch.empty((J, 1 << dims, N), dtype=torch.float32, device=dev) if want_rows else None
+    rc = lib.cobalt_ale(X.data_ptr(), N, F, X.stride(0), gf.nodes.data_ptr(), gf.tree_ptr.data_ptr(),
+                        gf.tile_ptr.data_ptr(), gf.n_tiles, gf.tile_cap, b.base_margin, desc.ctypes.data,
+                        jd.data_ptr(), J, dims, ed.data_ptr(), off, _native.ptr(weights), _native.ptr(order),
+                        _native.ptr(seg), max_cells, _native.ptr(rows), _native.ptr(work), _native.ptr(sums), stream)
+    _native.check(rc, "cobalt_ale")
+    return rows, sums
+
+
+def accumulated_local_effects(b: Booster, X, jobs, edges, *, n_trees: int | None = None, weights=None,
+                              device=None) -> list[dict]:
+    """The ALE sums of every job (a tuple of one or two feature indices, with one edge vector per feature; one-
+    and two-feature jobs may be mixed), as NumPy: per job ``{"sum_margin", "sum_prob", "weight": float64 [K1] or
+    [K1, K2], "n_missing": int}`` (``models.booster.ale_curve`` turns them into curves). A CUDA device runs
+    ``csrc/ale.hip``, all jobs of a kind in one launch series; the CPU runs
+    :func:`~..models.booster.ale_host` (the definition) job by job."""
+    d = _device_of(X, device)
+    w32 = None if weights is None else _host_vec(weights)
+    jobs = [tuple(int(f) for f in (j if isinstance(j, (tuple, list)) else (j,))) for j in jobs]
+    out: list[dict | None] = [None] * len(jobs)
+    if d.type != "cuda":
+        Xn = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
+        for i, (feats, ez) in enumerate(zip(jobs, edges)):
+            ez = [ez] if len(feats) == 1 and not isinstance(ez, (tuple, list)) else list(ez)
+            r = ale_host(b, Xn, feats, ez, n_trees, w32)
+            out[i] = {k: r[k] for k in ("sum_margin", "sum_prob", "weight", "n_missing")}
+        return out
+    Xt = _as_f32(X, d)
+    N = Xt.shape[0]
+    if w32 is not None and w32.shape[0] != N:
+        raise ValueError(f"X has {N} rows, weights has {w32.shape[0]}")
+    wt = None if w32 is None else torch.as_tensor(w32, device=d)
+    per = max(1, min(ALE_MAX_JOBS, ALE_JOB_ENTRIES // max(N, 1)))
+    for dims in (1, 2):
+        ids = [i for i, feats in enumerate(jobs) if len(feats) == dims]
+        for g0 in range(0, len(ids), per):
+            grp = ids[g0:g0 + per]
+            gj, ge = _check_ale_args(b, [jobs[i] for i in grp], [edges[i] for i in grp])
+            _, sums = accumulated_local_effects_gpu(b, Xt, gj, ge, n_trees=n_trees, weights=wt, want_rows=False,
+                                                    want_sums=True)
+            nan = torch.isnan(Xt)
+            miss = torch.stack([nan[:, list(feats)].any(dim=1).sum() for feats in gj]).cpu().numpy()
+            s = sums.cpu().numpy()
+            for q, i in enumerate(grp):
+                shape = tuple(len(z) - 1 for z in ge[q])
+                c = s[q, :int(np.prod(shape))]
+                out[i] = {"sum_margin": c[:, 0].reshape(shape).copy(), "sum_prob": c[:, 1].reshape(shape).copy(),
+                          "weight": c[:, 2].reshape(shape).copy(), "n_missing": int(miss[q])}
+    if any(o is None for o in out):
+        raise ValueError("an ALE job takes one or two features")
+    return out
 
 
 # ------------------------------------------------------------------- leaf indices and leaf refresh
