@@ -10,6 +10,7 @@ Commands mirror the reference's scripts:
   train-nn  NN challenger (notebook 04 cells 31-44)
   serve     FastAPI scoring service (cobalt_fast_api.py, uvicorn)
   dictionary  descriptions of columns from the LendingClub data dictionary workbook (LCDataDictionary.xlsx)
+  drift     population-stability (PSI / CSI) report of one CSV against another (monitor/drift.py)
 
 The artifact store is ``--store`` or ``$COBALT_ARTIFACT_URI`` (a local directory or ``s3://bucket``).
 """
@@ -159,6 +160,45 @@ def cmd_dictionary(args) -> int:
     return 0
 
 
+def cmd_drift(args) -> int:
+    """PSI / CSI of CUR.csv against REF.csv (monitor/drift.py): the report as JSON, the top rows on stdout."""
+    import pandas as pd
+    import torch
+
+    from .monitor import DriftBaseline
+
+    ref, cur = pd.read_csv(args.ref), pd.read_csv(args.cur)
+    model = None
+    if args.model:
+        from .models.booster import Booster
+
+        model = Booster.load_model(args.model)
+    if model is not None and model.feature_names:
+        cols = list(model.feature_names)
+    else:
+        num = [c for c in ref.columns if c in cur.columns and pd.api.types.is_numeric_dtype(ref[c])
+               and pd.api.types.is_numeric_dtype(cur[c])]
+        cols = [c for c in num if c != args.label]
+    if not cols:
+        raise SystemExit("no numeric column is common to both files")
+    y_ref = ref[args.label].to_numpy() if args.label and args.label in ref.columns else None
+    y_cur = cur[args.label].to_numpy() if args.label and args.label in cur.columns else None
+
+    def mat(df):
+        X = df[cols].to_numpy(dtype="float32", na_value=float("nan"))
+        dev = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
+        return torch.as_tensor(X, device=dev) if str(dev).startswith("cuda") else X
+
+    base = DriftBaseline.fit(mat(ref), feature_names=cols, model=model, n_bins=args.bins, y=y_ref)
+    rep = base.compare(mat(cur), y=y_cur)
+    with open(args.out, "w") as fh:
+        json.dump(rep.to_dict(), fh)
+    for r in list(rep)[:args.top]:
+        print(f"{r['feature']}\t{r['psi']:.6f}\t{r['status']}")
+    print(f"[INFO] wrote {args.out} ({len(rep)} rows)")
+    return 0
+
+
 def main(argv: list[str] | None = None) -> int:
     logging.basicConfig(level=logging.INFO, format="[%(levelname)s] %(message)s")
     p = argparse.ArgumentParser(prog="cobalt_smart_lender_ai_amd")
@@ -206,6 +246,15 @@ def main(argv: list[str] | None = None) -> int:
     s.add_argument("--xlsx", required=True, help="path to LCDataDictionary.xlsx")
     s.add_argument("columns", nargs="*")
     s.set_defaults(fn=cmd_dictionary)
+    s = sub.add_parser("drift", help="PSI / CSI drift report of CUR.csv against REF.csv")
+    s.add_argument("ref")
+    s.add_argument("cur")
+    s.add_argument("--model", default=None, help="model checkpoint: adds the score row, fixes the columns")
+    s.add_argument("--bins", type=int, default=10)
+    s.add_argument("--label", default=None, help="label column (adds WoE / IV per side)")
+    s.add_argument("--out", default="drift.json")
+    s.add_argument("--top", type=int, default=10, help="rows printed")
+    s.set_defaults(fn=cmd_drift)
     args = p.parse_args(argv)
     return args.fn(args)
 

@@ -35,5 +35,25 @@ def feature_importance_figure(names: list[str], importances: np.ndarray, top: in
     return fig
 
 
+def drift_plot(report, top: int = 20):
+    """Horizontal bars of the ``top`` largest PSI values of a ``monitor.DriftReport`` (rows are already sorted,
+    ``"score"`` first), with the 0.1 ("moderate" from here) and 0.25 ("shifted") lines."""
+    from ..monitor.drift import PSI_SHIFTED, PSI_STABLE
+
+    rows = list(report)[:top]
+    if not rows:
+        raise ValueError("nothing to draw")
+    colors = {"stable": "#4daf4a", "moderate": "#ff7f00", "shifted": "#e41a1c"}
+    fig, ax = plt.subplots(figsize=(8, max(2.5, 0.32 * len(rows) + 1.2)))
+    ax.barh([r["feature"] for r in rows][::-1], [r["psi"] for r in rows][::-1],
+            color=[colors[r["status"]] for r in rows][::-1])
+    ax.axvline(PSI_STABLE, color="grey", lw=1.0, ls="--")
+    ax.axvline(PSI_SHIFTED, color="black", lw=1.0, ls="--")
+    ax.set_xlabel("Population stability index")
+    ax.set_title("Drift against the baseline")
+    fig.tight_layout()
+    return fig
+
+
 def close(fig) -> None:
     plt.close(fig)
