@@ -11,6 +11,7 @@ Commands mirror the reference's scripts:
   serve     FastAPI scoring service (cobalt_fast_api.py, uvicorn)
   dictionary  descriptions of columns from the LendingClub data dictionary workbook (LCDataDictionary.xlsx)
   drift     population-stability (PSI / CSI) report of one CSV against another (monitor/drift.py)
+  bootstrap bootstrap confidence intervals of AUC, KS, ... from a CSV of labels and scores (metrics/bootstrap.py)
 
 The artifact store is ``--store`` or ``$COBALT_ARTIFACT_URI`` (a local directory or ``s3://bucket``).
 """
@@ -199,6 +200,32 @@ def cmd_drift(args) -> int:
     return 0
 
 
+def cmd_bootstrap(args) -> int:
+    """Bootstrap intervals (metrics/bootstrap.py) of the scores in SCORES.csv against its label column, and the
+    paired comparison when a second score column is named: the report as JSON on stdout."""
+    import pandas as pd
+    import torch
+
+    from .metrics import bootstrap_ci
+
+    df = pd.read_csv(args.csv)
+    for c in [args.label, args.score] + ([args.score_b] if args.score_b else []):
+        if c not in df.columns:
+            raise SystemExit(f"{args.csv} has no column {c!r}")
+    dev = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
+    rep = bootstrap_ci(df[args.label].to_numpy(), df[args.score].to_numpy(dtype="float32"),
+                       df[args.score_b].to_numpy(dtype="float32") if args.score_b else None,
+                       metrics=tuple(args.metrics.split(",")), n_boot=args.n_boot, alpha=args.alpha, seed=args.seed,
+                       threshold=args.threshold, device=dev)
+    d = rep.to_dict()
+    if not args.values:
+        for part in ("metrics", "metrics_b", "delta"):
+            for m in d.get(part, {}).values():
+                m.pop("values")
+    print(json.dumps(d))
+    return 0
+
+
 def main(argv: list[str] | None = None) -> int:
     logging.basicConfig(level=logging.INFO, format="[%(levelname)s] %(message)s")
     p = argparse.ArgumentParser(prog="cobalt_smart_lender_ai_amd")
@@ -255,6 +282,19 @@ def main(argv: list[str] | None = None) -> int:
     s.add_argument("--out", default="drift.json")
     s.add_argument("--top", type=int, default=10, help="rows printed")
     s.set_defaults(fn=cmd_drift)
+    s = sub.add_parser("bootstrap", help="bootstrap confidence intervals from a CSV of labels and scores")
+    s.add_argument("csv")
+    s.add_argument("--label", default="label", help="0/1 label column")
+    s.add_argument("--score", default="score", help="score column of the model")
+    s.add_argument("--score-b", default=None, help="score column of a second model: adds the paired comparison")
+    s.add_argument("--metrics", default="auc,ks", help="comma-separated: auc,gini,ks,error,precision,recall,f1,"
+                                                       "logloss,brier")
+    s.add_argument("--n-boot", type=int, default=1000)
+    s.add_argument("--alpha", type=float, default=0.05)
+    s.add_argument("--seed", type=int, default=0)
+    s.add_argument("--threshold", type=float, default=0.5)
+    s.add_argument("--values", action="store_true", help="keep every replicate's value in the JSON")
+    s.set_defaults(fn=cmd_bootstrap)
     args = p.parse_args(argv)
     return args.fn(args)
 

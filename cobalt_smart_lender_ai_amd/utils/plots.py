@@ -55,5 +55,44 @@ def drift_plot(report, top: int = 20):
     return fig
 
 
+def ci_plot(report):
+    """Point estimates with their bootstrap percentile intervals, one row per metric of a
+    ``metrics.BootstrapReport``: model a, model b when the report has one, and a second panel with the paired
+    differences a - b against the zero line."""
+    names = list(report.metrics)
+    if not names:
+        raise ValueError("nothing to draw")
+    paired = report.metrics_b is not None
+    fig, axes = plt.subplots(1, 2 if paired else 1, figsize=(11 if paired else 7, max(2.5, 0.5 * len(names) + 1.2)),
+                             squeeze=False)
+    ypos = np.arange(len(names))[::-1].astype(float)
+
+    def bars(ax, rows, dy, color, label):
+        pt = np.array([r.point for r in rows], dtype=float)
+        lo = np.array([r.low for r in rows], dtype=float)
+        hi = np.array([r.high for r in rows], dtype=float)
+        ax.errorbar(pt, ypos + dy, xerr=[np.nan_to_num(pt - lo), np.nan_to_num(hi - pt)], fmt="o", color=color,
+                    capsize=3, label=label)
+
+    ax = axes[0, 0]
+    bars(ax, [report.metrics[m] for m in names], 0.12 if paired else 0.0, "#377eb8", "a")
+    if paired:
+        bars(ax, [report.metrics_b[m] for m in names], -0.12, "#ff7f00", "b")
+        ax.legend(loc="best")
+    ax.set_yticks(ypos)
+    ax.set_yticklabels(names)
+    pct = 100.0 * (1.0 - report.alpha)
+    ax.set_title(f"{pct:g}% bootstrap intervals ({report.n_boot} replicates)")
+    if paired:
+        ax = axes[0, 1]
+        bars(ax, [report.delta[m] for m in names], 0.0, "#4daf4a", "a - b")
+        ax.axvline(0.0, color="black", lw=1.0, ls="--")
+        ax.set_yticks(ypos)
+        ax.set_yticklabels(names)
+        ax.set_title("Paired difference a - b")
+    fig.tight_layout()
+    return fig
+
+
 def close(fig) -> None:
     plt.close(fig)
