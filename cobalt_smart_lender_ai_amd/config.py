@@ -145,7 +145,7 @@ KNOBS: dict[str, Knob] = {
     "COBALT_HIST_ABLATE": Knob("0", "native", "timing-only ablations of the histogram / partition / root passes (wrong models)"),
     "COBALT_HIST_CHUNK": Knob("auto", "native", "rows per histogram work item at levels >= 1 (~n/1536, 1024..4096)"),
     "COBALT_HIST_CHUNK0": Knob("auto", "native", "rows per root histogram item when the root pass is not fused"),
-    "COBALT_ROOT_CHUNK": Knob("auto", "native", "rows per item of the fused gradient + root-histogram pass (whole rounds of 2 blocks per CU)"),
+    "COBALT_ROOT_CHUNK": Knob("auto", "native", "rows per item of the fused gradient + root-histogram pass (auto: whole rounds of the resident blocks, 2 or 3 per CU by the pass's data mode)"),
     "COBALT_PART_CHUNK": Knob("auto", "native", "rows per partition item (4096 while a level fits one block per CU, else 8192; <= 8192)"),
     "COBALT_EVAL_FG": Knob("auto", "native", "features per split-evaluation group (0 = one block per node; 8 above 32 features)"),
     "COBALT_EVAL_PART": Knob("1", "native", "split evaluation fused into the partition pass while a level fits one block per CU (0 off, 2 forced)"),

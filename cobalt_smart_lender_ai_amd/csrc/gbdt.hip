@@ -931,7 +931,7 @@ __device__ __forceinline__ HistLanes hist_lanes_finish(const HistLaneRaw& raw, i
 
 
 // Add one 32-byte record (bins in a.xyzw / b.xy, packed (g, h) in b.wz) to the LDS histogram.
-// Per feature: byte extract, clamp, shift-add, ds_add_u64 (3 VALU ops per atomic). The missing code
+// Per feature: byte extract + clamp (one SDWA v_min), shift-add, ds_add_u64 (2 VALU ops per atomic). The missing code
 // 255 clamps to cell nbins, which the layout keeps inside the feature's 256 cells and the flush never
 // reads (a 256-bin feature has no missing values: its code 255 is a real bin); features masked out by
 // colsample, and the tile's padding up to FT4 (= features rounded up to 4), add into a trash cell.
@@ -959,6 +959,54 @@ __device__ __forceinline__ void hist_add_rec32(uint64_t* s_hist, const HistLanes
         atomicAdd(reinterpret_cast<unsigned long long*>(base + off), (unsigned long long)gp);
       }
     }
+  }
+}
+
+// The same cells as hist_add_rec32 (17-bit pairs) with no per-feature VGPR: the lane's copy is merged into
+// the cell index by one v_and_or -- byte offset = fl * 2048 | bin << (sh + 3) | (lane << 3 & copy mask) -- from
+// per-feature uniform values, and the feature's base is an immediate of the ds_add. 20 features hold 20
+// registers less than HistLanes::lb8, which is what fits the root pass's record modes into 80 VGPRs.
+// A feature masked out by colsample adds into bin 0 of its OWN 64 copies-worth of cells (the flush never reads
+// a masked feature); the tile's padding features (fl >= ft, at most the last three) into the trash cells.
+struct HistLanesLean {
+  uint32_t lane8;      // lane << 3
+  uint32_t fm[24];     // nbins | (copy shift + 3) << 16; nbins 0 (masked / padding): 64 copies of bin 0
+};
+
+template <int FT4>
+__device__ __forceinline__ HistLanesLean hist_lanes_lean(const uint32_t* s_fm) {
+  HistLanesLean hl;
+  hl.lane8 = (uint32_t)lane_id() << 3;
+#pragma unroll
+  for (int fl = 0; fl < FT4; ++fl) {
+    const uint32_t m = hist_meta_of(s_fm, fl);
+    hl.fm[fl] = (m & 0xffffu) ? m : (9u << 16);
+  }
+  return hl;
+}
+
+template <int FT4>
+__device__ __forceinline__ void hist_add_rec32_lean(uint64_t* s_hist, const HistLanesLean& hl, int ft, const uint4& a,
+                                                    const uint4& b) {
+  static_assert(FT4 % 4 == 0 && FT4 > 0 && FT4 <= 24, "32-byte records hold <= 24 bins");
+  const uint32_t hz = b.z & 0x7FFFFFFFu;  // (bit 31: the label, lab31 records)
+  const uint64_t gp = ((uint64_t)b.w << 32) | hz;
+  char* base = reinterpret_cast<char*>(s_hist);
+  // (opaque to the optimiser: it would hoist every feature's `lane8 & mk8` out of the row loop, one VGPR each)
+  uint32_t lane8 = hl.lane8;
+  asm volatile("" : "+v"(lane8));
+#pragma unroll
+  for (int fl = 0; fl < FT4; ++fl) {
+    const uint32_t m = hl.fm[fl];
+    const int q = fl >> 2;
+    const uint32_t word = q == 0 ? a.x : q == 1 ? a.y : q == 2 ? a.z : q == 3 ? a.w : q == 4 ? b.x : b.y;
+    const uint32_t bb = (word >> (8 * (fl & 3))) & 0xffu;
+    const uint32_t sh3 = (m >> 16) & 15u;
+    const uint32_t mk8 = (1u << sh3) - 8u;  // (copies - 1) << 3
+    const uint32_t off = (lane8 & mk8) | (min(bb, m & 0xffffu) << sh3);  // (disjoint bits: v_and_or_b32)
+    // (F > FT4 - 4, so only the last three features of the tile can be padding)
+    char* cell = fl <= FT4 - 4 ? (base + fl * (kMaxBins * 8)) + off : (base + min(fl, ft) * (kMaxBins * 8)) + off;
+    atomicAdd(reinterpret_cast<unsigned long long*>(cell), (unsigned long long)gp);
   }
 }
 
@@ -995,7 +1043,7 @@ __device__ __forceinline__ void flush_meta_store(const FlushMeta& m, int ft, int
 }
 
 template <bool kWide = false>
-__device__ void hist_flush(const GbdtDev& d, const uint64_t* s_hist, const HistLanes& hl, int item, int f0, int ft,
+__device__ void hist_flush(const GbdtDev& d, const uint64_t* s_hist, uint32_t lane, int item, int f0, int ft,
                            int64_t tg, int64_t th, bool tot_block, int64_t (*s_tot)[16], const int* s_fo,
                            const int* s_fs) {
   // Each cell finds its feature by a binary search over the LDS-staged offsets and sums its copies.
@@ -1026,7 +1074,7 @@ __device__ void hist_flush(const GbdtDev& d, const uint64_t* s_hist, const HistL
   if (tot_block) {
     tg = wave_sum(tg);
     th = wave_sum(th);
-    if (hl.lane == 0) { s_tot[0][wave_id()] = tg; s_tot[1][wave_id()] = th; }
+    if (lane == 0) { s_tot[0][wave_id()] = tg; s_tot[1][wave_id()] = th; }
     __syncthreads();
     if (threadIdx.x == 0) {
       int64_t G = 0, H = 0;
@@ -1037,61 +1085,22 @@ __device__ void hist_flush(const GbdtDev& d, const uint64_t* s_hist, const HistL
   }
 }
 
-// Gradients fused with the ROOT histogram (32-byte records, one feature tile): the gradient pass
-// already streams every record, so the level-0 LDS histogram is accumulated from the registers
-// holding the freshly quantised (g, h) and the bins -- the separate root histogram pass (a full
-// 32 B/row re-read) disappears. Block b = root work item b: rows [b*chunk, (b+1)*chunk).
-// Also: previous-tree margin update + archive and node-table init, as k_grad.
-// kWide: wide gradients (16-byte LDS cells {g, h}, 25-bit quantisation).
+// The fused root pass (grad_hist_body below) compiles its per-row loop for a data mode kMode; the host picks
+// it per launch (root_mode):
+//   kRootGeneric  every mode by run-time flags (margin / label / weight arrays or record fields, subsample,
+//                 either store form, the timing-only ablations, wide cells, data parallel);
+//   kRootRec      margin and label bit in the record (mrec, ylab, lab31), rows in their original order,
+//                 no subsampling, one GPU: the per-row state is the record alone;
+//   kRootRecOrig  the same after a row reorder (the hashes' key is loaded from orig).
+// The two record modes carry no margin / label / weight / orig-or-not state and no subsample hash through
+// the loop, which is what lets them run 3 blocks per CU (k_grad_hist).
+constexpr int kRootGeneric = 0, kRootRec = 1, kRootRecOrig = 2;
+
+// The root pass's row loop, every data mode by run-time flags (kRootGeneric).
 template <int U, int FT4, bool kWide>
-__device__ __forceinline__ void grad_hist_body(const GbdtDev& d, int tree, int apply_tree, int chunk) {
-  constexpr int kW = kWide ? 2 : 1;            // u64 words per LDS cell
-  constexpr uint32_t kCs = kWide ? 4u : 3u;    // log2 of the cell bytes
-  BlockStamp stamp_(d);
-  extern __shared__ uint64_t s_dyn[];
-  __shared__ int64_t s_tot[2][16];
-  __shared__ int s_fo[kMaxFeatTile + 1], s_fs[kMaxFeatTile];
-  __shared__ uint32_t s_fm[kWave];
-  const int ft = d.F;
-  const int entries = ft * kMaxBins + kWave;  // one tile: tile_entries[0] == F * 256
-  // independent metadata loads first (they share the round trip of the previous tree's node table)
-  const HistLaneRaw lraw = hist_lanes_load(d, tree, 0, ft);
-  const FlushMeta fmeta = flush_meta_load(d, tree, 0, ft);
-  uint64_t* s_hist = s_dyn;
-  uint4* s_walk = reinterpret_cast<uint4*>(s_dyn + entries * kW);  // the previous tree (stage_walk)
-  {  // zero the root histogram slot (k_hist_reduce accumulates into it)
-    int4* zp = reinterpret_cast<int4*>(d.zero_red ? d.zero_red : d.hist_b[0]);
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < d.slot_elems / 2;
-         e += (int64_t)gridDim.x * blockDim.x)
-      zp[e] = make_int4(0, 0, 0, 0);
-  }
-  if (apply_tree >= 0) {
-    stage_walk(d, d.prev_nodes, s_walk);
-    const int4* src = reinterpret_cast<const int4*>(d.prev_nodes);
-    int4* dst = reinterpret_cast<int4*>(d.trees + (int64_t)apply_tree * d.max_nodes);
-    const int nv = d.max_nodes * (int)(sizeof(Node) / sizeof(int4));
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nv; e += gridDim.x * blockDim.x) dst[e] = src[e];
-  }
-  if (blockIdx.x == 0) {
-    init_tree_block(d);
-    if (threadIdx.x == 0) d.counters[0] = gridDim.x;
-  }
-  for (int i = threadIdx.x; i < entries * kW; i += blockDim.x) s_hist[i] = 0ull;
-  flush_meta_store(fmeta, ft, s_fo, s_fs);
-  hist_meta_store(lraw, s_fm, kCs);
-  __syncthreads();
-  stamp_.probe(1);
-  const int item = blockIdx.x;
-  const int64_t begin = (int64_t)item * chunk, end = min(d.n, begin + chunk);
-  if (threadIdx.x == 0) {
-    WorkItem w;
-    w.node = 0; w.slot = 0; w.begin = (int32_t)begin; w.end = (int32_t)end;
-    d.items_h[item] = w;
-  }
-  const HistLanes hl = hist_lanes_finish(lraw, ft, s_fm, kCs);
-  const uint64_t tree_key = tree_key_of(d.seed, tree);
-  const uint64_t dkey = splitmix64(tree_key ^ kDitherSalt);
-  int64_t tg = 0, th = 0;
+__device__ __forceinline__ void root_rows_generic(const GbdtDev& d, int apply_tree, const uint4* s_walk, uint64_t* s_hist,
+                                                  const HistLanes& hl, uint64_t tree_key, uint64_t dkey, int64_t begin,
+                                                  int64_t end, int64_t& tg, int64_t& th) {
   const int B = blockDim.x;
   for (int64_t i0 = begin + threadIdx.x; i0 < end; i0 += U * B) {
     uint4 ra[U], rb[U];
@@ -1160,9 +1169,129 @@ __device__ __forceinline__ void grad_hist_body(const GbdtDev& d, int tree, int a
       if (d.ablate != 21) hist_add_rec32<FT4, kWide>(s_hist, hl, ra[u], rb[u]);  // (21: timing-only, no LDS atomics)
     }
   }
+}
+
+// The root pass's row loop in the record modes (kRootRec, kRootRecOrig).
+template <int U, int FT4, int kMode>
+__device__ __forceinline__ void root_rows_rec(const GbdtDev& d, int apply_tree, const uint4* s_walk, uint64_t* s_hist,
+                                              const HistLanesLean& hl, uint64_t dkey, int64_t begin, int64_t end,
+                                              int64_t& tg, int64_t& th) {
+  const int B = blockDim.x;
+  // Record modes: margin in word 5, label in bit 31 of word 6, weight from the label. The mode flags,
+  // the margin / label / weight arrays, the subsample hash, the write-through store form and the
+  // ablation switches do not exist here.
+  const bool walk = apply_tree >= 0;
+  for (int64_t i0 = begin + threadIdx.x; i0 < end; i0 += U * B) {
+    uint4 ra[U], rb[U];
+    int32_t og[kMode == kRootRecOrig ? U : 1];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + (int64_t)u * B;
+      const int64_t ii = i < end ? i : begin;
+      const uint4* rec = reinterpret_cast<const uint4*>(d.bins + ii * 32);
+      ra[u] = rec[0];
+      rb[u] = rec[1];
+      if constexpr (kMode == kRootRecOrig) og[u] = d.orig[ii];  // (loaded with the record)
+    }
+    float lf[U];
+    if (walk) walk_leaves<U>(s_walk, d.max_depth, ra, rb, lf);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + (int64_t)u * B;
+      if (i >= end) continue;
+      float mf = __int_as_float((int)rb[u].y);
+      if (walk) mf += lf[u];
+      const double mm = (double)mf;
+      const double p = 1.0 / (1.0 + exp(-mm));
+      const uint32_t lbit = rb[u].z & 0x80000000u;
+      const float yl = lbit ? 1.0f : 0.0f;
+      const float wt = yl != 0.0f ? d.spw : 1.0f;
+      const double y = (double)yl;
+      const double w = (double)wt;
+      const double g = (p - y) * w;
+      const double h = fmax(p * (1.0 - p), 1e-16) * w;
+      // the hashes' key: the global row (one GPU: row_offset == 0; original order: the position itself,
+      // no register per row in flight)
+      const int64_t gi = kMode == kRootRecOrig ? (int64_t)og[u] : (int64_t)(int32_t)i;
+      int64_t gq, hq;
+      quantize_gh(g, h, d.gscale, d.hscale, dkey, gi, gq, hq, false);
+      tg += gq;
+      th += hq;
+      rb[u].y = (uint32_t)__float_as_int(mf);
+      rb[u].z = (uint32_t)hq | lbit;
+      rb[u].w = (uint32_t)(int32_t)gq;
+      reinterpret_cast<uint4*>(d.bins + i * 32)[1] = rb[u];
+      hist_add_rec32_lean<FT4>(s_hist, hl, d.F, ra[u], rb[u]);
+    }
+  }
+}
+
+// Gradients fused with the ROOT histogram (32-byte records, one feature tile): the gradient pass
+// already streams every record, so the level-0 LDS histogram is accumulated from the registers
+// holding the freshly quantised (g, h) and the bins -- the separate root histogram pass (a full
+// 32 B/row re-read) disappears. Block b = root work item b: rows [b*chunk, (b+1)*chunk).
+// Also: previous-tree margin update + archive and node-table init, as k_grad.
+// kWide: wide gradients (16-byte LDS cells {g, h}, 25-bit quantisation). kMode: see kRootGeneric.
+template <int U, int FT4, bool kWide, int kMode>
+__device__ __forceinline__ void grad_hist_body(const GbdtDev& d, int tree, int apply_tree, int chunk) {
+  static_assert(kMode == kRootGeneric || !kWide, "the record modes are 17-bit");
+  constexpr int kW = kWide ? 2 : 1;            // u64 words per LDS cell
+  constexpr uint32_t kCs = kWide ? 4u : 3u;    // log2 of the cell bytes
+  BlockStamp stamp_(d);
+  extern __shared__ uint64_t s_dyn[];
+  __shared__ int64_t s_tot[2][16];
+  __shared__ int s_fo[kMaxFeatTile + 1], s_fs[kMaxFeatTile];
+  __shared__ uint32_t s_fm[kWave];
+  const int ft = d.F;
+  const int entries = ft * kMaxBins + kWave;  // one tile: tile_entries[0] == F * 256
+  // independent metadata loads first (they share the round trip of the previous tree's node table)
+  const HistLaneRaw lraw = hist_lanes_load(d, tree, 0, ft);
+  const FlushMeta fmeta = flush_meta_load(d, tree, 0, ft);
+  uint64_t* s_hist = s_dyn;
+  uint4* s_walk = reinterpret_cast<uint4*>(s_dyn + entries * kW);  // the previous tree (stage_walk)
+  {  // zero the root histogram slot (k_hist_reduce accumulates into it)
+    int4* zp = reinterpret_cast<int4*>(d.zero_red ? d.zero_red : d.hist_b[0]);
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < d.slot_elems / 2;
+         e += (int64_t)gridDim.x * blockDim.x)
+      zp[e] = make_int4(0, 0, 0, 0);
+  }
+  if (apply_tree >= 0) {
+    stage_walk(d, d.prev_nodes, s_walk);
+    const int4* src = reinterpret_cast<const int4*>(d.prev_nodes);
+    int4* dst = reinterpret_cast<int4*>(d.trees + (int64_t)apply_tree * d.max_nodes);
+    const int nv = d.max_nodes * (int)(sizeof(Node) / sizeof(int4));
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nv; e += gridDim.x * blockDim.x) dst[e] = src[e];
+  }
+  if (blockIdx.x == 0) {
+    init_tree_block(d);
+    if (threadIdx.x == 0) d.counters[0] = gridDim.x;
+  }
+  for (int i = threadIdx.x; i < entries * kW; i += blockDim.x) s_hist[i] = 0ull;
+  flush_meta_store(fmeta, ft, s_fo, s_fs);
+  hist_meta_store(lraw, s_fm, kCs);
+  __syncthreads();
+  stamp_.probe(1);
+  const int item = blockIdx.x;
+  const int64_t begin = (int64_t)item * chunk, end = min(d.n, begin + chunk);
+  if (threadIdx.x == 0) {
+    WorkItem w;
+    w.node = 0; w.slot = 0; w.begin = (int32_t)begin; w.end = (int32_t)end;
+    d.items_h[item] = w;
+  }
+  int64_t tg = 0, th = 0;
+  if constexpr (kMode != kRootGeneric) {
+    const HistLanesLean hl = hist_lanes_lean<FT4>(s_fm);
+    const uint64_t dkey = splitmix64(tree_key_of(d.seed, tree) ^ kDitherSalt);
+    root_rows_rec<U, FT4, kMode>(d, apply_tree, s_walk, s_hist, hl, dkey, begin, end, tg, th);
+  } else {
+    const HistLanes hl = hist_lanes_finish(lraw, ft, s_fm, kCs);
+    const uint64_t tree_key = tree_key_of(d.seed, tree);
+    const uint64_t dkey = splitmix64(tree_key ^ kDitherSalt);
+    root_rows_generic<U, FT4, kWide>(d, apply_tree, s_walk, s_hist, hl, tree_key, dkey, begin, end, tg, th);
+  }
   __syncthreads();
   stamp_.probe(2);
-  hist_flush<kWide>(d, s_hist, hl, item, 0, ft, tg, th, true, s_tot, s_fo, s_fs);
+  hist_flush<kWide>(d, s_hist, (uint32_t)lane_id(), item, 0, ft, tg, th, true, s_tot, s_fo, s_fs);
 }
 
 // U rows in flight per thread; 2 per CU of 512 threads at 95 VGPRs (no waves-per-EU bound: capping U = 2
@@ -1170,7 +1299,16 @@ __device__ __forceinline__ void grad_hist_body(const GbdtDev& d, int tree, int a
 // (wide cells: 1024-thread blocks -- the 16-byte-cell tile holds a CU to one block, so twice the waves)
 template <int U, int FT4, bool kWide = false>
 __global__ __launch_bounds__(kWide ? 1024 : 512) void k_grad_hist(GbdtDev d, int tree, int apply_tree, int chunk) {
-  grad_hist_body<U, FT4, kWide>(d, tree, apply_tree, chunk);
+  grad_hist_body<U, FT4, kWide, kRootGeneric>(d, tree, apply_tree, chunk);
+}
+
+// The record modes (kRootRec, kRootRecOrig): 78-79 VGPRs, 3 blocks of 512 threads per CU = 6 waves per SIMD
+// while the LDS allows it (20 features at depth 7: 3 x (41.5 KB tile + 8 KB staged tree + 1 KB) = 148 KB of
+// 160; a deeper tree's staging leaves 2). grow_impl sizes the grid from the runtime's occupancy for the kernel.
+template <int U, int FT4, int kMode>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k_grad_hist_rec(GbdtDev d, int tree, int apply_tree,
+                                                                                               int chunk) {
+  grad_hist_body<U, FT4, false, kMode>(d, tree, apply_tree, chunk);
 }
 
 
@@ -1430,7 +1568,7 @@ __global__ __launch_bounds__(kWide ? kHistThreadsWide : kHistThreads) __attribut
   // Per-item partial histogram -> slab (plain coalesced stores; the packed u64 of the K copies can
   // be summed directly because the per-item sums obey the same < 2^31 / < 2^32 bounds).
   if (d.ablate == 2) return;  // timing-only: no flush
-  hist_flush<kWide>(d, s_hist, hl, item, f0, ft, tg, th, blockIdx.y == 0, s_tot, s_fo, s_fs);
+  hist_flush<kWide>(d, s_hist, hl.lane, item, f0, ft, tg, th, blockIdx.y == 0, s_tot, s_fo, s_fs);
 }
 
 // Reduce the per-item slabs into the level's histogram slots: thread = one compact (feature, bin)
@@ -3088,8 +3226,12 @@ struct GbdtCtx {
   ConsDev cons{};
   // the last grow call's plan (cobalt_gbdt_plan): fused IPC exchange, ownership level, wide gradients,
   // resident blocks of the fused k_eval, levels run by the fused evaluation + partition pass (and of them
-  // the evaluator-block levels, and those whose grid exceeds one block per CU)
-  int32_t plan[7] = {0, -1, 0, 0, 0, 0, 0};
+  // the evaluator-block levels, and those whose grid exceeds one block per CU), the fused root pass's data mode
+  // (kRootGeneric / kRootRec / kRootRecOrig; -1: no fused root pass) and the resident blocks per CU its grid was sized for
+  int32_t plan[9] = {0, -1, 0, 0, 0, 0, 0, -1, 0};
+  // resident blocks per CU of the root pass's record-mode kernels with this layout's LDS ([kRootRec - 1],
+  // [kRootRecOrig - 1]; set_layout asks the runtime once per layout). 0: no record kernel for this layout
+  int root_rec_per_cu[2] = {0, 0};
   unsigned* err_pinned = nullptr;  // mapped host word behind d.err_host
   // COBALT_STAMPS=<file>: per-launch in-kernel timing of every grow call, appended to <file>
   const char* stamp_path = nullptr;
@@ -3269,6 +3411,29 @@ static GradHistKernel grad_hist_kernel(int ft4, bool wide = false) {
     case 20: return k_grad_hist<2, 20, false>;
     case 24: return k_grad_hist<2, 24, false>;
     default: return nullptr;
+  }
+}
+// The root pass's data mode for this launch (grad_hist_body): a record mode when the per-row state is the
+// record alone, else the generic instantiation (it also serves the timing-only ablations).
+static int root_mode(const GbdtDev& d, int ft4) {
+  const bool rec = d.mrec && d.ylab && d.lab31 && !d.wide && !d.dp && d.row_offset == 0 && !(d.subsample < 1.0) &&
+                   d.ablate == 0 && ft4 >= 12 && ft4 <= 20;
+  return !rec ? kRootGeneric : d.orig ? kRootRecOrig : kRootRec;
+}
+template <int kMode>
+static GradHistKernel grad_hist_rec_kernel(int ft4) {
+  switch (ft4) {  // (32-byte records hold 9 .. 24 features, and the label bit needs F <= 20)
+    case 12: return k_grad_hist_rec<2, 12, kMode>;
+    case 16: return k_grad_hist_rec<2, 16, kMode>;
+    case 20: return k_grad_hist_rec<2, 20, kMode>;
+    default: return nullptr;
+  }
+}
+static GradHistKernel root_kernel(const GbdtDev& d, int ft4, int mode) {
+  switch (mode) {
+    case kRootRec: return grad_hist_rec_kernel<kRootRec>(ft4);
+    case kRootRecOrig: return grad_hist_rec_kernel<kRootRecOrig>(ft4);
+    default: return grad_hist_kernel(ft4, d.wide != 0);
   }
 }
 
@@ -3519,6 +3684,21 @@ COBALT_API int cobalt_gbdt_set_data(void* h, uint8_t* bins, const uint8_t* binsT
   if (grad_hist_lds > 64 * 1024 && grad_hist_kernel(hist_ft4(c->d), wide))
     CK(hipFuncSetAttribute((const void*)grad_hist_kernel(hist_ft4(c->d), wide),
                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)grad_hist_lds));
+  // the root pass's record-mode kernels of this feature count: the same opt-in, and their resident blocks per
+  // CU with this LDS (the root grid's whole-rounds rule, grow_impl). A kernel that cannot be resident is an error.
+  c->root_rec_per_cu[0] = c->root_rec_per_cu[1] = 0;
+  const int ft4 = hist_ft4(c->d);
+  if (!wide && !c->cfg.comm && ft4 >= 12 && ft4 <= 20) {  // (a data-parallel context never runs a record mode)
+    const GradHistKernel rk[2] = {grad_hist_rec_kernel<kRootRec>(ft4), grad_hist_rec_kernel<kRootRecOrig>(ft4)};
+    for (int m = 0; m < 2; ++m) {
+      if (grad_hist_lds > 64 * 1024)
+        CK(hipFuncSetAttribute((const void*)rk[m], hipFuncAttributeMaxDynamicSharedMemorySize, (int)grad_hist_lds));
+      int per_cu = 0;
+      CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)rk[m], 512, grad_hist_lds));
+      if (per_cu < 1) return -19;
+      c->root_rec_per_cu[m] = per_cu;
+    }
+  }
   return 0;
 }
 
@@ -3706,12 +3886,19 @@ static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool s
   static const int env_root = knob_int(Knob::RootChunk, 0);
   // (never more root items than the work-item buffers hold)
   const int root_min = (int)((ceil_div(d.n, (int64_t)c->items_cap - 8) + 63) / 64 * 64);
-  // Fused root pass: whole rounds of resident blocks (2 per CU at 95 VGPRs x 512 threads) of ~8k rows;
-  // a partial last round idles CUs (10M rows: 8192-row items = 2.4 rounds, 9792-row items = 2 rounds:
-  // 167.5 -> 158.3 us per tree in the stamps)
+  // Fused root pass: whole rounds of resident blocks of ~8k rows; a partial last round idles CUs (10M rows,
+  // 2 blocks per CU: 8192-row items = 2.4 rounds, 9792-row items = 2 rounds: 167.5 -> 158.3 us per tree in
+  // the stamps). Resident blocks per CU: 2 for the generic instantiation (~100 VGPRs x 512 threads), for a
+  // record mode what the runtime reported for the kernel that will run with its LDS (set_layout; 3 on MI355X).
+  const int rmode = fuse_root ? root_mode(d, ft4) : -1;
+  const GradHistKernel root_k = fuse_root ? root_kernel(d, ft4, rmode) : nullptr;
+  const int root_per_cu = rmode > kRootGeneric ? c->root_rec_per_cu[rmode - 1] : 2;
+  if (fuse_root && (!root_k || root_per_cu < 1)) return -19;
+  c->plan[7] = rmode;
+  c->plan[8] = fuse_root ? root_per_cu : 0;
   int root_rule = std::min(chunk_hist(d, 0), 8192);
   if (fuse_root) {
-    const int64_t res = 2LL * device_cu_count();
+    const int64_t res = (int64_t)root_per_cu * device_cu_count();
     const int64_t rounds = std::max<int64_t>(1, (d.n + res * 4096) / (res * 8192));  // nearest to n / (res * 8192)
     root_rule = (int)std::min<int64_t>(16384, std::max<int64_t>(1024, (ceil_div(d.n, rounds * res) + 63) / 64 * 64));
   }
@@ -3738,7 +3925,7 @@ static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool s
       GLAUNCH("k_tree_begin", k_tree_begin, dim3(std::max(1, std::min(64, ceil_div(d.slot_elems / 2, 256)))), dim3(256), 0,
               stream, d);
     else if (fuse_root)
-      GLAUNCH("k_grad_hist", grad_hist_kernel(ft4, d.wide != 0), dim3(ceil_div(d.n, root_chunk)), dim3(d.wide ? 1024 : 512), c->lds_hist + walk_lds,
+      GLAUNCH("k_grad_hist", root_k, dim3(ceil_div(d.n, root_chunk)), dim3(d.wide ? 1024 : 512), c->lds_hist + walk_lds,
               stream, d, t, apply, root_chunk);
     else
       GLAUNCH("k_grad", k_grad, dim3(std::max(grad_grid, 1)), dim3(256), tree_lds, stream, d, t, apply);
@@ -4510,7 +4697,7 @@ COBALT_API int cobalt_gbdt_set_start(void* h, int t0) {
 // those the levels whose grid exceeds one block per CU.
 COBALT_API int cobalt_gbdt_plan(void* h, int32_t* out) {
   GbdtCtx* c = static_cast<GbdtCtx*>(h);
-  for (int k = 0; k < 7; ++k) out[k] = c->plan[k];
+  for (int k = 0; k < 9; ++k) out[k] = c->plan[k];
   return 0;
 }
 

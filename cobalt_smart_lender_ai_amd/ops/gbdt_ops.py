@@ -235,13 +235,18 @@ class GpuGbdtTrainer:
         fn = getattr(self.lib, "cobalt_gbdt_plan", None)
         if fn is None or not self.h:
             return {}
-        out = (ctypes.c_int32 * 7)()
+        out = (ctypes.c_int32 * 9)()
+        out[7] = -1  # (a library from before the root pass's data modes writes 7 words)
         fn(self.h, out)
         return {"ipc_fused": bool(out[0]), "own_level": int(out[1]), "wide_gradients": bool(out[2]),
                 "fused_eval_resident_blocks": int(out[3]),
                 "eval_part_levels": [lv for lv in range(16) if (out[4] >> lv) & 1],
                 "eval_block_levels": [lv for lv in range(16) if (out[5] >> lv) & 1],
-                "eval_block_overflow_levels": [lv for lv in range(16) if (out[6] >> lv) & 1]}
+                "eval_block_overflow_levels": [lv for lv in range(16) if (out[6] >> lv) & 1],
+                # the fused root pass (csrc/gbdt.hip grad_hist_body): its data mode in the last grow call
+                # (None: no fused root pass) and the resident blocks per CU its grid was sized for
+                "root_mode": {0: "generic", 1: "rec", 2: "rec_orig"}.get(int(out[7])),
+                "root_blocks_per_cu": int(out[8])}
 
     def replica_error(self) -> int:
         """Data-parallel replica check (csrc/gbdt.hip GbdtDev::dig): 0 = healthy, 2 = this rank's trees
