@@ -12,6 +12,8 @@ Commands mirror the reference's scripts:
   dictionary  descriptions of columns from the LendingClub data dictionary workbook (LCDataDictionary.xlsx)
   drift     population-stability (PSI / CSI) report of one CSV against another (monitor/drift.py)
   bootstrap bootstrap confidence intervals of AUC, KS, ... from a CSV of labels and scores (metrics/bootstrap.py)
+  calibration reliability report (ECE, Brier decomposition, Hosmer-Lemeshow) of a CSV of labels and probabilities,
+            and optionally an isotonic / sigmoid calibrator fitted on it (metrics/calibration.py)
 
 The artifact store is ``--store`` or ``$COBALT_ARTIFACT_URI`` (a local directory or ``s3://bucket``).
 """
@@ -226,6 +228,37 @@ def cmd_bootstrap(args) -> int:
     return 0
 
 
+def cmd_calibration(args) -> int:
+    """The reliability report (metrics/calibration.py) of the probabilities in SCORES.csv against its label
+    column, as JSON on stdout. With --fit, a calibrator is fitted on the log-odds of that column, written to
+    --out, and the report of the calibrated probabilities is printed beside the first ("calibrated")."""
+    import numpy as np
+    import pandas as pd
+    import torch
+
+    from .metrics.calibration import reliability_report
+    from .models.calibration import make_calibrator
+
+    df = pd.read_csv(args.csv)
+    for c in (args.label, args.score):
+        if c not in df.columns:
+            raise SystemExit(f"{args.csv} has no column {c!r}")
+    dev = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
+    y = torch.as_tensor(df[args.label].to_numpy()).to(dev)
+    p = torch.as_tensor(df[args.score].to_numpy(dtype="float32")).to(dev)
+    d = reliability_report(y, p, n_bins=args.bins, strategy=args.strategy).to_dict()
+    if args.fit:
+        p64 = p.to(torch.float64).clamp(1e-12, 1 - 1e-12)
+        margin = (torch.log(p64) - torch.log1p(-p64)).to(torch.float32)
+        cal = make_calibrator(args.fit).fit(margin, y)
+        cal.save(args.out)
+        d["calibrated"] = reliability_report(y, cal.transform(margin), n_bins=args.bins,
+                                             strategy=args.strategy).to_dict()
+        d["calibrator"] = args.out
+    print(json.dumps(d))
+    return 0
+
+
 def main(argv: list[str] | None = None) -> int:
     logging.basicConfig(level=logging.INFO, format="[%(levelname)s] %(message)s")
     p = argparse.ArgumentParser(prog="cobalt_smart_lender_ai_amd")
@@ -295,6 +328,17 @@ def main(argv: list[str] | None = None) -> int:
     s.add_argument("--threshold", type=float, default=0.5)
     s.add_argument("--values", action="store_true", help="keep every replicate's value in the JSON")
     s.set_defaults(fn=cmd_bootstrap)
+    s = sub.add_parser("calibration", help="reliability report (and a fitted calibrator) from a CSV of labels and "
+                                           "probabilities")
+    s.add_argument("csv")
+    s.add_argument("--label", default="label", help="0/1 label column")
+    s.add_argument("--score", default="score", help="probability column of the model")
+    s.add_argument("--bins", type=int, default=10)
+    s.add_argument("--strategy", default="quantile", choices=["quantile", "uniform"])
+    s.add_argument("--fit", default=None, choices=["isotonic", "sigmoid"],
+                   help="fit this calibrator on the column's log-odds and report the calibrated scores too")
+    s.add_argument("--out", default="calibration.json", help="where --fit writes the calibrator")
+    s.set_defaults(fn=cmd_calibration)
     args = p.parse_args(argv)
     return args.fn(args)
 

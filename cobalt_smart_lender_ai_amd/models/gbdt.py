@@ -1403,6 +1403,40 @@ class GBDTClassifier:
                 setattr(new, k, getattr(self, k))
         return new
 
+    def _binary_labels(self, y):
+        if isinstance(y, torch.Tensor):
+            return y
+        y_np = np.asarray(y.to_numpy() if hasattr(y, "to_numpy") else y).reshape(-1)
+        classes = getattr(self, "classes_", None)
+        if classes is not None and len(classes) == 2 and not np.isin(y_np, (0, 1)).all():
+            if not np.isin(y_np, classes).all():
+                raise ValueError("labels must be among the training classes")
+            return (y_np == classes[-1]).astype(np.int64)
+        return y_np
+
+    def calibrate(self, X=None, y=None, method: str = "isotonic", sample_weight=None):
+        """A :class:`models.calibration.CalibratedModel`: this classifier with a calibrator fitted on its margin
+        over the held-out rows ``(X, y)``. ``method``: "isotonic", "sigmoid" (Platt) or "prior" (the analytic
+        inverse of ``scale_pos_weight``; ``X`` and ``y`` may be None). CUDA tensors are fitted on their device.
+        This estimator and its ``predict_proba`` are unchanged."""
+        from .calibration import CalibratedModel, make_calibrator
+
+        b = self.get_booster()
+        cal = make_calibrator(method, float(self._train_params().scale_pos_weight))
+        if method != "prior":
+            if X is None or y is None:
+                raise ValueError(f"method {method!r} needs held-out rows X and labels y")
+            margin = b.predict_margin(self._matrix(X), device=self.device, n_trees=self._n_trees(None))
+            cal.fit(margin, self._binary_labels(y), sample_weight)
+        return CalibratedModel(self, cal)
+
+    def reliability(self, X, y, **kw):
+        """``metrics.calibration.reliability_report`` of this model's ``prob_default`` on ``(X, y)``."""
+        from ..metrics.calibration import reliability_report
+
+        p = self.get_booster().predict_proba(self._matrix(X), device=self.device, n_trees=self._n_trees(None))
+        return reliability_report(self._binary_labels(y), p, **kw)
+
     def score(self, X, y) -> float:
         from ..metrics.classification import accuracy_score
 

@@ -94,5 +94,33 @@ def ci_plot(report):
     return fig
 
 
+def reliability_plot(report):
+    """The reliability diagram of a ``metrics.calibration.ReliabilityReport``: the diagonal, the observed rate
+    against the mean predicted probability of every non-empty bin, and below it the bins' counts."""
+    live = ~np.isnan(np.asarray(report.mean_predicted, dtype=float))
+    if not live.any():
+        raise ValueError("nothing to draw")
+    mp = np.asarray(report.mean_predicted, dtype=float)[live]
+    ob = np.asarray(report.observed, dtype=float)[live]
+    fig, axes = plt.subplots(2, 1, figsize=(6, 7), sharex=True, gridspec_kw={"height_ratios": [3, 1]})
+    ax = axes[0]
+    ax.plot([0.0, 1.0], [0.0, 1.0], color="black", lw=1.0, ls="--", label="perfectly calibrated")
+    ax.plot(mp, ob, "o-", color="#377eb8", label="model")
+    ax.set_ylabel("Observed rate")
+    ax.set_xlim(0.0, 1.0)
+    ax.set_ylim(0.0, 1.0)
+    ax.set_title(f"Reliability ({report.n_bins} {report.strategy} bins): ECE {report.ece:.4f}, "
+                 f"Brier {report.brier:.4f}")
+    ax.legend(loc="upper left")
+    ax = axes[1]
+    edges = np.concatenate([[0.0], np.asarray(report.edges, dtype=float), [1.0]])
+    ax.bar(edges[:-1], np.asarray(report.count, dtype=float), width=np.maximum(np.diff(edges), 1e-3), align="edge",
+           color="#999999", edgecolor="white")
+    ax.set_xlabel("Predicted probability")
+    ax.set_ylabel("Count")
+    fig.tight_layout()
+    return fig
+
+
 def close(fig) -> None:
     plt.close(fig)
