@@ -22,6 +22,10 @@
 //    and a whole tree (or fit) can be enqueued back to back / captured in a hipGraph.
 //  * Data parallel: the only cross-rank traffic is one int64 SUM all-reduce of the built
 //    histogram slots per level, issued on the same stream through a native RCCL communicator.
+//
+// One translation unit. This file holds the in-core trainer; what is not part of its level loop is included where
+// it is needed: gbdt_bin.h (binning), gbdt_ooc.h (sampled external-memory page pass), gbdt_ox.h (exact
+// external-memory mode, after the host context).
 #include "common.h"
 #include "comm.h"
 #include "gbdt_math.h"
@@ -311,53 +315,7 @@ struct BlockStamp {
   }
 };
 
-// ------------------------------------------------------------------------------------------
-// Binning: X fp32 [N][F] (row-major, NaN = missing) -> uint8 bins (row-major + feature-major)
-// bin(x) = #cuts <= x (upper_bound), clamped to nbins-1; NaN -> 255.
-// ------------------------------------------------------------------------------------------
-template <bool CUTS_IN_LDS>
-__global__ __launch_bounds__(256) void k_bin(const float* __restrict__ X, int64_t n, int F, int64_t ldx,
-                                             const float* __restrict__ cuts, const int32_t* __restrict__ nbins,
-                                             uint8_t* __restrict__ bins, int stride,
-                                             uint8_t* __restrict__ binsT, int64_t ldt) {
-  extern __shared__ float s_cuts[];
-  if (CUTS_IN_LDS) {
-    for (int i = threadIdx.x; i < F * kMaxBins; i += blockDim.x) s_cuts[i] = cuts[i];
-    __syncthreads();
-  }
-  const float* C = CUTS_IN_LDS ? s_cuts : cuts;
-  for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < n;
-       row += (int64_t)gridDim.x * blockDim.x) {
-    const float* x = X + row * ldx;
-    uint32_t word = 0;
-    const int fw = (F + 3) & ~3;  // bytes written per row (the record tail holds the gradient pair)
-    for (int f = 0; f < fw; ++f) {
-      uint32_t b = 0;
-      if (f < F) {
-        float v = x[f];
-        const int nb = nbins[f];
-        if (v != v) {
-          b = kMissingBin;
-        } else {
-          // upper_bound over cuts[f][0..nb)
-          const float* c = C + f * kMaxBins;
-          int lo = 0, hi = nb;
-          while (lo < hi) {
-            int mid = (lo + hi) >> 1;
-            if (c[mid] <= v) lo = mid + 1; else hi = mid;
-          }
-          b = lo >= nb ? (uint32_t)(nb - 1) : (uint32_t)lo;
-        }
-        binsT[(int64_t)f * ldt + row] = (uint8_t)b;
-      }
-      word |= b << (8 * (f & 3));
-      if ((f & 3) == 3) {
-        *reinterpret_cast<uint32_t*>(bins + row * stride + (f & ~3)) = word;
-        word = 0;
-      }
-    }
-  }
-}
+#include "gbdt_bin.h"
 
 // ------------------------------------------------------------------------------------------
 // Per-tree initialisation + binary:logistic gradients (K14)
@@ -606,154 +564,17 @@ __global__ __launch_bounds__(256) void k_tree_begin(GbdtDev d) {
   if (blockIdx.x == 0) init_tree_block(d);
 }
 
-// ------------------------------------------------------------------------------------------
-// External-memory training (BASELINE.json config "100M-row out-of-core GBDT with
-// host-DRAM spill"). The quantised row records live in host memory as pages; per tree every page
-// streams through k_ooc_page, which
-//   * applies the previous tree to the rows' margins (margins / labels / weights stay on the device),
-//   * computes binary:logistic g, h (fp64, as k_grad) and ghat = sqrt(g^2 + h^2),
-//   * keeps a minimal-variance sample (MVS -- the sampler of XGBoost's gradient_based external
-//     memory mode): row i with probability p_i = min(1, ghat_i / mu), its pair reweighted by 1/p_i
-//     (unbiased histograms; |g/p|, h/p <= mu, so the fixed-point scales hold when mu <= w_max),
-//   * compacts kept rows into the trainer's row records + feature-major bins (one wave-aggregated
-//     claim per wave; the order is irrelevant because every histogram sum is an exact integer),
-//   * counts ghat in kOocBins log-spaced bins (binary exponent x 16 mantissa steps, exact integer
-//     counts -> the host derives the next mu deterministically, models/external.py).
-// The in-core trainer then grows the tree on the sample (cobalt_gbdt_grow_sampled).
-// ------------------------------------------------------------------------------------------
-constexpr int kOocBins = 2048;
-
-__device__ __forceinline__ int ooc_bin(double v) {
-  if (!(v > 0.0)) return 0;
-  int e;
-  const double f = frexp(v, &e);  // v = f * 2^e, f in [0.5, 1)
-  const int b = (e + 64) * 16 + (int)floor((f - 0.5) * 32.0);
-  return b < 1 ? 1 : (b >= kOocBins ? kOocBins - 1 : b);
+// Binary labels into the row records (see GbdtDev::ylab): after set_data, for a fit whose labels are
+// all 0 or 1 and whose weights are 1 (negatives) or `spw` (positives) -- the caller checks both. Writes
+// byte 23 of every record (padding: bins occupy bytes 0..F-1, F <= 23 -- for F > 20 the histogram reads
+// byte 23 as a padding feature's bin, which goes to the trash cell -- and the gradient pass rewrites
+// bytes 16..31 from the record it read). Saves 8 of the ~80 bytes per row the gradient pass moves.
+__global__ __launch_bounds__(256) void k_put_label(uint8_t* bins, const float* label, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    bins[i * 32 + 23] = label[i] != 0.0f ? 1 : 0;
 }
 
-// `ps` = page row stride in bytes: 32 (full row records) or the compact spill format, the F bins
-// rounded up to 4 bytes (20 B for the 20 deployed features: 37% less PCIe traffic per tree -- the
-// per-tree page stream is bound by the H2D copy).
-__global__ __launch_bounds__(256) void k_ooc_page(const uint8_t* __restrict__ page, int ps, int64_t n, int64_t r0, int F,
-                                                  const Node* __restrict__ prev, int max_nodes,
-                                                  float* __restrict__ margin, const float* __restrict__ label,
-                                                  const float* __restrict__ weight, uint64_t key, int64_t row_offset,
-                                                  double mu, double gscale, double hscale, uint8_t* __restrict__ srec,
-                                                  uint8_t* __restrict__ sbinsT, int64_t cap,
-                                                  unsigned long long* __restrict__ counter,
-                                                  unsigned int* __restrict__ hist) {
-  __shared__ uint32_t s_meta[2047];
-  __shared__ float s_leaf[2047];
-  __shared__ unsigned int s_h[kOocBins];
-  for (int i = threadIdx.x; i < kOocBins; i += blockDim.x) s_h[i] = 0u;
-  if (prev != nullptr)
-    for (int i = threadIdx.x; i < max_nodes; i += blockDim.x) {
-      const Node nd = prev[i];
-      s_meta[i] = node_meta(nd);
-      s_leaf[i] = nd.leaf_value;
-    }
-  __syncthreads();
-  const int lane = lane_id();
-  // wave-uniform loop (ballots below): every lane of a wave iterates the same bases
-  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < n; base += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = base + threadIdx.x;
-    const bool in = i < n;
-    bool keep = false;
-    uint4 ra = make_uint4(0, 0, 0, 0), rb = make_uint4(0, 0, 0, 0);
-    if (in) {
-      if (ps == 32) {
-        const uint4* rec = reinterpret_cast<const uint4*>(page + i * 32);
-        ra = rec[0];
-        rb = rec[1];
-        rb.z = rb.w = 0u;  // (g, h) slot: rewritten below for kept rows
-      } else {  // compact page: ps / 4 bin words, the rest of the record is zero padding
-        const uint32_t* rw = reinterpret_cast<const uint32_t*>(page + i * ps);
-        const int nw = ps >> 2;
-        ra.x = rw[0];
-        if (nw > 1) ra.y = rw[1];
-        if (nw > 2) ra.z = rw[2];
-        if (nw > 3) ra.w = rw[3];
-        if (nw > 4) rb.x = rw[4];
-        if (nw > 5) rb.y = rw[5];
-      }
-      float mf = margin[r0 + i];
-      if (prev != nullptr) {
-        int nx = 0;
-        uint32_t m = s_meta[0];
-        while (m & kMetaSplit) {
-          const int f = m & 0xFFFF, q = f >> 2;
-          const uint32_t word = q == 0 ? ra.x : q == 1 ? ra.y : q == 2 ? ra.z : q == 3 ? ra.w : q == 4 ? rb.x : rb.y;
-          const uint32_t b = (word >> (8 * (f & 3))) & 0xffu;
-          const bool left = meta_left(m, b);
-          nx = 2 * nx + (left ? 1 : 2);
-          m = s_meta[nx];
-        }
-        mf += s_leaf[nx];
-        margin[r0 + i] = mf;
-      }
-      const double p = 1.0 / (1.0 + exp(-(double)mf));
-      const double y = (double)label[r0 + i], w = (double)weight[r0 + i];
-      const double g = (p - y) * w;
-      const double h = fmax(p * (1.0 - p), 1e-16) * w;
-      const double gh = sqrt(g * g + h * h);
-      atomicAdd(&s_h[ooc_bin(gh)], 1u);
-      if (mu > 0.0) {
-        const double pk = gh >= mu ? 1.0 : gh / mu;
-        keep = uniform01(splitmix64(key ^ (uint64_t)(row_offset + r0 + i))) < pk;
-        if (keep) {
-          int64_t gq = (int64_t)rint(g / pk * gscale), hq = (int64_t)rint(h / pk * hscale);
-          gq = gq > 65536 ? 65536 : (gq < -65536 ? -65536 : gq);
-          hq = hq > 65536 ? 65536 : (hq < 0 ? 0 : hq);
-          rb.z = (uint32_t)hq;
-          rb.w = (uint32_t)(int32_t)gq;
-        }
-      }
-    }
-    const uint64_t km = __ballot(keep);
-    if (km) {
-      const int leader = __ffsll((unsigned long long)km) - 1;
-      unsigned long long b0 = 0;
-      if (lane == leader) b0 = atomicAdd(counter, (unsigned long long)__popcll(km));
-      b0 = (unsigned long long)readlane64((int64_t)b0, leader);
-      if (keep) {
-        const int64_t slot = (int64_t)b0 + mask_rank(km);
-        if (slot < cap) {
-          uint4* dst = reinterpret_cast<uint4*>(srec + slot * 32);
-          dst[0] = ra;
-          dst[1] = rb;
-          for (int f = 0; f < F; ++f) {
-            const int q = f >> 2;
-            const uint32_t word = q == 0 ? ra.x : q == 1 ? ra.y : q == 2 ? ra.z : q == 3 ? ra.w : q == 4 ? rb.x : rb.y;
-            sbinsT[(int64_t)f * cap + slot] = (uint8_t)((word >> (8 * (f & 3))) & 0xffu);
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < kOocBins; i += blockDim.x)
-    if (s_h[i]) atomicAdd(&hist[i], s_h[i]);
-}
-
-COBALT_API int cobalt_ooc_page(const uint8_t* page, int page_stride, int64_t n, int64_t r0, int F, const void* prev,
-                               int max_nodes,
-                               float* margin, const float* label, const float* weight, uint64_t key,
-                               int64_t row_offset, double mu, double gscale, double hscale, uint8_t* srec,
-                               uint8_t* sbinsT, int64_t cap, unsigned long long* counter, unsigned int* hist,
-                               hipStream_t stream) {
-  if (F < 1 || F > 24 || max_nodes > 2047 || n < 0) return -3;  // 32-byte records only
-  if (page_stride != 32 && (page_stride % 4 != 0 || page_stride < F || page_stride > 24)) return -3;
-  if (n == 0) return 0;
-  const int grid = std::max(1, std::min(ceil_div(n, 256), 256 * 8));
-  hipLaunchKernelGGL(k_ooc_page, dim3(grid), dim3(256), 0, stream, page, page_stride, n, r0, F,
-                     static_cast<const Node*>(prev),
-                     max_nodes, margin, label, weight, key, row_offset, mu, gscale, hscale, srec, sbinsT, cap, counter,
-                     hist);
-  CK_LAUNCH();
-  return 0;
-}
-
-COBALT_API int cobalt_ooc_bins() { return kOocBins; }
+#include "gbdt_ooc.h"
 
 // ------------------------------------------------------------------------------------------
 // Self-planning work lists. A pass over the rows of several nodes is cut into items of at most
@@ -3201,6 +3022,20 @@ __global__ __launch_bounds__(1024) void k_eval_part(GbdtDev d, int parity, int64
 extern "C" int cobalt_comm_allreduce_sum_i64(void* comm, int64_t* buf, int64_t count, hipStream_t stream);
 extern "C" int cobalt_comm_allreduce(void* comm, void* buf, int64_t count, int dtype, int op, hipStream_t stream);
 
+// Entries of the exported launch plan (cobalt_gbdt_plan; ops/gbdt_ops.py GpuGbdtTrainer.plan reads them in this order)
+enum PlanIdx {
+  kPlanIpcFused,    // fused IPC exchange
+  kPlanOwnLevel,    // node-ownership level (-1 off)
+  kPlanWide,        // wide gradients
+  kPlanResident,    // blocks of the fused k_eval this rank's CUs hold at once
+  kPlanEpLevels,    // bit mask of the levels run by the fused evaluation + partition pass
+  kPlanEbLevels,    // ... of them in the evaluator-block form
+  kPlanEbOverflow,  // ... of those, the levels whose grid (evaluators + items) exceeds one block per CU
+  kPlanRootMode,    // the fused root pass's data mode (kRootGeneric / kRootRec / kRootRecOrig; -1: no fused root pass)
+  kPlanRootPerCu,   // ... and the resident blocks per CU its grid was sized for (0 without a fused root pass)
+  kPlanCount
+};
+
 struct GbdtCtx {
   GbdtConfig cfg{};
   GbdtDev d{};
@@ -3224,11 +3059,8 @@ struct GbdtCtx {
   // ones: the features' group words and the nodes' compat words (cons.inter)
   bool inter_on = false;
   ConsDev cons{};
-  // the last grow call's plan (cobalt_gbdt_plan): fused IPC exchange, ownership level, wide gradients,
-  // resident blocks of the fused k_eval, levels run by the fused evaluation + partition pass (and of them
-  // the evaluator-block levels, and those whose grid exceeds one block per CU), the fused root pass's data mode
-  // (kRootGeneric / kRootRec / kRootRecOrig; -1: no fused root pass) and the resident blocks per CU its grid was sized for
-  int32_t plan[9] = {0, -1, 0, 0, 0, 0, 0, -1, 0};
+  // the last grow call's plan as cobalt_gbdt_plan exports it (PlanIdx; export_plan)
+  int32_t plan[kPlanCount] = {0, -1, 0, 0, 0, 0, 0, -1, 0};
   // resident blocks per CU of the root pass's record-mode kernels with this layout's LDS ([kRootRec - 1],
   // [kRootRecOrig - 1]; set_layout asks the runtime once per layout). 0: no record kernel for this layout
   int root_rec_per_cu[2] = {0, 0};
@@ -3275,20 +3107,6 @@ static int stamp_next(GbdtCtx* c, const char* name) {
   do {                                  \
     c->d.seq = stamp_next(c, tag);      \
     hipLaunchKernelGGL(__VA_ARGS__);    \
-  } while (0)
-// The constrained kernels' instantiation for the fit: monotone, interaction or both (arguments as GLAUNCH's
-// after the kernel).
-#define CONS_EVAL(kGroups, ...)                                                                        \
-  do {                                                                                                 \
-    if (c->mono_on && c->inter_on) GLAUNCH("k_eval", (k_eval_mono<kGroups, true, true>), __VA_ARGS__); \
-    else if (c->inter_on) GLAUNCH("k_eval", (k_eval_mono<kGroups, false, true>), __VA_ARGS__);         \
-    else GLAUNCH("k_eval", (k_eval_mono<kGroups, true, false>), __VA_ARGS__);                          \
-  } while (0)
-#define CONS_FINISH(...)                                                                                     \
-  do {                                                                                                       \
-    if (c->mono_on && c->inter_on) GLAUNCH("k_eval_finish", (k_eval_finish_mono<true, true>), __VA_ARGS__);  \
-    else if (c->inter_on) GLAUNCH("k_eval_finish", (k_eval_finish_mono<false, true>), __VA_ARGS__);          \
-    else GLAUNCH("k_eval_finish", (k_eval_finish_mono<true, false>), __VA_ARGS__);                           \
   } while (0)
 
 // Trees whose launches are stamped: every 64th from tree 5 (and tree 0 of short fits).
@@ -3415,8 +3233,9 @@ static GradHistKernel grad_hist_kernel(int ft4, bool wide = false) {
 }
 // The root pass's data mode for this launch (grad_hist_body): a record mode when the per-row state is the
 // record alone, else the generic instantiation (it also serves the timing-only ablations).
-static int root_mode(const GbdtDev& d, int ft4) {
-  const bool rec = d.mrec && d.ylab && d.lab31 && !d.wide && !d.dp && d.row_offset == 0 && !(d.subsample < 1.0) &&
+// (`mrec`, `dp`: the call's plan, which GbdtDev takes over after it)
+static int root_mode(const GbdtDev& d, int ft4, bool mrec, bool dp) {
+  const bool rec = mrec && d.ylab && d.lab31 && !d.wide && !dp && d.row_offset == 0 && !(d.subsample < 1.0) &&
                    d.ablate == 0 && ft4 >= 12 && ft4 <= 20;
   return !rec ? kRootGeneric : d.orig ? kRootRecOrig : kRootRec;
 }
@@ -3435,6 +3254,55 @@ static GradHistKernel root_kernel(const GbdtDev& d, int ft4, int mode) {
     case kRootRecOrig: return grad_hist_rec_kernel<kRootRecOrig>(ft4);
     default: return grad_hist_kernel(ft4, d.wide != 0);
   }
+}
+
+// Split-evaluation kernels: grouped (features in groups over several blocks, then k_eval_finish) or one block
+// per node; over the fused IPC exchange, data parallel, or one GPU. A constrained fit (monotone, interaction or
+// both) runs kernels of its own, which take the constraints as one more argument.
+typedef void (*EvalKernel)(GbdtDev, int, int, int, int, EvalSlots);
+typedef void (*ConsEvalKernel)(GbdtDev, int, int, int, int, EvalSlots, ConsDev);
+typedef void (*EvalFinishKernel)(GbdtDev, int, int, int);
+typedef void (*ConsFinishKernel)(GbdtDev, int, int, int, ConsDev);
+static EvalKernel eval_kernel(bool groups, bool fused, bool dp) {
+  if (groups) return fused ? k_eval<true, true, true> : dp ? k_eval<true, false, true> : k_eval<true, false, false>;
+  return fused ? k_eval<false, true, true> : dp ? k_eval<false, false, true> : k_eval<false, false, false>;
+}
+static ConsEvalKernel cons_eval_kernel(bool groups, bool mono, bool inter) {
+  if (groups)
+    return mono && inter ? k_eval_mono<true, true, true>
+           : inter       ? k_eval_mono<true, false, true>
+                         : k_eval_mono<true, true, false>;
+  return mono && inter ? k_eval_mono<false, true, true>
+         : inter       ? k_eval_mono<false, false, true>
+                       : k_eval_mono<false, true, false>;
+}
+static EvalFinishKernel eval_finish_kernel(bool dp) { return dp ? k_eval_finish<true> : k_eval_finish<false>; }
+static ConsFinishKernel cons_finish_kernel(bool mono, bool inter) {
+  return mono && inter ? k_eval_finish_mono<true, true>
+         : inter       ? k_eval_finish_mono<false, true>
+                       : k_eval_finish_mono<true, false>;
+}
+// The level's evaluation launch (`fused_lds`: the exchange's LDS, used when this level's epoch is set) and the
+// grouped form's per-node reduction.
+static void launch_eval(GbdtCtx* c, bool groups, dim3 grid, dim3 block, size_t fused_lds, hipStream_t stream, int level,
+                        int parity, int t, int fg, const EvalSlots& es) {
+  const GbdtDev& d = c->d;
+  c->d.seq = stamp_next(c, "k_eval");
+  if (c->mono_on || c->inter_on)
+    hipLaunchKernelGGL(cons_eval_kernel(groups, c->mono_on, c->inter_on), grid, block, 0, stream, d, level, parity, t, fg,
+                       es, c->cons);
+  else
+    hipLaunchKernelGGL(eval_kernel(groups, d.ipc_epoch != 0, d.dp != 0), grid, block, d.ipc_epoch ? fused_lds : 0, stream,
+                       d, level, parity, t, fg, es);
+}
+static void launch_eval_finish(GbdtCtx* c, hipStream_t stream, int level, int parity, int ngroups) {
+  const GbdtDev& d = c->d;
+  c->d.seq = stamp_next(c, "k_eval_finish");
+  if (c->mono_on || c->inter_on)
+    hipLaunchKernelGGL(cons_finish_kernel(c->mono_on, c->inter_on), dim3(1 << level), dim3(kWave), 0, stream, d, level,
+                       parity, ngroups, c->cons);
+  else
+    hipLaunchKernelGGL(eval_finish_kernel(d.dp != 0), dim3(1 << level), dim3(kWave), 0, stream, d, level, parity, ngroups);
 }
 
 // Compute units of the current device (256 on MI355X), cached per process. COBALT_CU_BUDGET caps it
@@ -3725,90 +3593,88 @@ static void launch_eval_part(int steps, int mode, dim3 grid, size_t lds, hipStre
 #undef EP_LAUNCH
 }
 
-// Enqueue `n_trees` boosting rounds starting at tree index `t0`. No host synchronisation.
-// `sampled`: the row records already hold the (reweighted) gradient pairs of this tree's rows --
-// the external-memory path, where k_ooc_page wrote a fresh sample -- so the tree starts with a
-// node-table reset + a plain root histogram instead of the gradient pass, and no margins are kept.
-static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool sampled) {
-  GbdtDev& d = c->d;
+// Everything a grow call decides once, before its first launch (plan_grow); the enqueue functions only read it.
+struct GrowPlan {
+  bool dp;         // any native communicator turns on the data-parallel protocol (a 1-rank one exercises it on 1 GPU)
+  bool ipc;        // IPC one-shot group (ipccomm.hip): the reduce accumulates into this rank's exported send slot and
+                   // one exchange kernel per level writes the all-reduced histograms into hist_b (no RCCL call)
+  bool ipc_fused;  // ... the exchange fused into the split evaluation (k_eval, or k_eval_part's evaluator blocks)
+  bool sampled;    // grow_sampled: the records already hold this tree's gradient pairs
+  bool mono;       // monotone / interaction constraints: the constrained evaluation kernels
+  bool fuse_root;  // gradients + root histogram in one pass (32-byte records, one feature tile)
+  bool mrec;       // margins in the row records for this call (GbdtDev::mrec)
+  bool eval_part;  // split evaluation fused into the partition pass (k_eval_part) where ep[level].chunk > 0
+  bool part_pos;   // position-ordered partition blocks (k_part_pos); COBALT_PART_POS=0: node-ordered items
+  int ft4, ftiles, grad_grid;
+  int eval_fg;     // grouped split evaluation: features per block (0 = one 1024-thread block per node)
+  int own_level;   // node ownership from this level (-1 off; see node_owner)
+  int resident;    // blocks of the fused k_eval this rank's CUs hold at once
+  size_t fused_lds, tree_lds, walk_lds;
+  int root_mode, root_per_cu, root_chunk;  // the fused root pass: data mode (-1: none), blocks per CU, item rows
+  GradHistKernel root_kernel;
+  // A level's fused evaluation + partition pass: {item rows (0: separate k_eval + k_partition), mode}
+  struct { int chunk, mode; } ep[10];
+};
+
+// Decide how a grow call runs. Enqueues nothing and changes nothing: a refused call (-11, -14, -15, -16, -19)
+// leaves the stream and the context as they were.
+static int plan_grow(GbdtCtx* c, int t0, bool sampled, GrowPlan* out) {
+  const GbdtDev& d = c->d;
   const int D = d.max_depth;
-  const int grad_grid = std::min(ceil_div(d.n, 256), 256 * 16);
-  const int ftiles = ceil_div(d.F, d.feat_tile);
-  const size_t tree_lds = (size_t)c->max_nodes * 8;
-  const size_t walk_lds = (size_t)c->max_nodes * kWalkNodeBytes;  // k_grad_hist's staged tree (stage_walk)
+  GrowPlan p{};
   if (t0 != c->grown) return -11;  // trees must be grown in order
-  if (int rc = stamp_begin(c, stream)) return rc;
-  // any native communicator turns on the data-parallel protocol (a 1-rank one exercises it on 1 GPU)
-  const bool dp = c->cfg.comm != nullptr;
-  d.dp = dp ? 1 : 0;
-  // IPC one-shot group (ipccomm.hip): the reduce accumulates into this rank's exported send slot and
-  // one exchange kernel per level writes the all-reduced histograms into hist_b (no RCCL call)
+  p.sampled = sampled;
+  p.grad_grid = std::min(ceil_div(d.n, 256), 256 * 16);
+  p.ftiles = ceil_div(d.F, d.feat_tile);
+  p.tree_lds = (size_t)c->max_nodes * 8;
+  p.walk_lds = (size_t)c->max_nodes * kWalkNodeBytes;  // k_grad_hist's staged tree (stage_walk)
+  p.dp = c->cfg.comm != nullptr;
   CobaltComm* const cc = static_cast<CobaltComm*>(c->cfg.comm);
-  const bool ipc = dp && cc->kind == 2;
-  d.hist_red = nullptr;
-  if (ipc) {
-    if (ipc_capacity(cc) < ((int64_t)c->pairs_max * d.slot_elems + 2) * (int64_t)sizeof(int64_t)) {
-      comm_set_error("ipc: slot capacity below one level of histograms (raise COBALT_IPC_SLOT_MB)");
-      return -14;
-    }
-    if (int rc = ipc_zero_send(cc, d.slot_elems * (int64_t)sizeof(int64_t), stream)) return rc;
+  p.ipc = p.dp && cc->kind == 2;
+  if (p.ipc && ipc_capacity(cc) < ((int64_t)c->pairs_max * d.slot_elems + 2) * (int64_t)sizeof(int64_t)) {
+    comm_set_error("ipc: slot capacity below one level of histograms (raise COBALT_IPC_SLOT_MB)");
+    return -14;
   }
-  // gradients + root histogram in one pass (32-byte records, one feature tile)
-  const int ft4 = hist_ft4(d);
-  const bool fuse_root = !sampled && ft4 > 0 && ftiles == 1 && (d.ablate == 0 || d.ablate >= 10);
+  p.ft4 = hist_ft4(d);
+  p.fuse_root = !sampled && p.ft4 > 0 && p.ftiles == 1 && (d.ablate == 0 || d.ablate >= 10);
   if (d.wide && sampled) return -15;  // (the sampled pages carry 17-bit pairs)
-  // margins in the row records for this call (GbdtDev::mrec) from 4M rows: 10M 231.9 / 234.2 vs 235.9 / 235.9
+  // margins in the row records from 4M rows: 10M 231.9 / 234.2 vs 235.9 / 235.9
   // ms per fit; at 1.25M the copy-in / copy-out launches and the lost write-through of (g, h) cost more
   // (78.2 / 78.9 vs 77.2 / 77.0; profiles/round6/ab_margin_in_record.txt). COBALT_MARGIN_IN_RECORD: 0 off,
   // 2 at any size
   const int env_mrec = knob_int(Knob::MarginInRecord, 1);  // (per call: a test switches it between fits)
-  d.mrec = (env_mrec != 0 && d.lab31 && fuse_root && d.n > 0 && (env_mrec == 2 || d.n >= 4000000)) ? 1 : 0;
-  {
-    const dim3 g1(std::max(1, std::min(ceil_div(d.n, 256), 4096)));
-    if (c->label_pending && d.mrec)
-      hipLaunchKernelGGL(k_margin_label_in, g1, dim3(256), 0, stream, d.bins, d.margin, d.label, d.n);
-    else if (c->label_pending)
-      hipLaunchKernelGGL(k_put_label31, g1, dim3(256), 0, stream, d.bins, d.label, d.n);
-    else if (d.mrec)
-      hipLaunchKernelGGL(k_margin_in, g1, dim3(256), 0, stream, d.bins, d.margin, d.n);
-    if (c->label_pending || d.mrec) CK_LAUNCH();
-    c->label_pending = false;
-  }
-  // grouped split evaluation: features per block (0 = one 1024-thread block per node); at most 64
-  // groups per node, at most 32 features per group (16 waves x 2). COBALT_EVAL_FG overrides.
+  p.mrec = env_mrec != 0 && d.lab31 && p.fuse_root && d.n > 0 && (env_mrec == 2 || d.n >= 4000000);
+  // at most 64 groups per node, at most 32 features per group (16 waves x 2). COBALT_EVAL_FG overrides.
   static const int env_fg = knob_int(Knob::EvalFg, -1);
-  int eval_fg = env_fg >= 0 ? env_fg : (d.F > 32 ? 8 : 0);
-  if (eval_fg == 0 && d.F > 32) eval_fg = 8;  // one k_eval block evaluates at most 32 features
-  if (eval_fg > 0) eval_fg = std::min(32, std::max(eval_fg, ceil_div(d.F, 64)));
+  p.eval_fg = env_fg >= 0 ? env_fg : (d.F > 32 ? 8 : 0);
+  if (p.eval_fg == 0 && d.F > 32) p.eval_fg = 8;  // one k_eval block evaluates at most 32 features
+  if (p.eval_fg > 0) p.eval_fg = std::min(32, std::max(p.eval_fg, ceil_div(d.F, 64)));
   // IPC exchange fused into the split evaluation (k_eval publishes, waits and sums the ranks' slots
   // itself: one launch per level fewer); COBALT_IPC_FUSED=0 keeps the separate exchange kernel
   const int env_ipc_fused = knob_int(Knob::IpcFused, 1);
   // LDS of the fused k_eval: the block's cells (+ the totals cell) summed over the ranks
-  int fused_cells = c->d.ncells;
-  if (eval_fg > 0) {
+  int fused_cells = d.ncells;
+  if (p.eval_fg > 0) {
     fused_cells = 0;
-    for (int f0 = 0; f0 < d.F; f0 += eval_fg)
-      fused_cells = std::max(fused_cells, c->hoff_h[std::min(d.F, f0 + eval_fg)] - c->hoff_h[f0]);
+    for (int f0 = 0; f0 < d.F; f0 += p.eval_fg)
+      fused_cells = std::max(fused_cells, c->hoff_h[std::min(d.F, f0 + p.eval_fg)] - c->hoff_h[f0]);
   }
-  const size_t fused_lds = (size_t)(fused_cells + 2) * 16;  // + the totals and the level-0 digest cells
+  p.fused_lds = (size_t)(fused_cells + 2) * 16;  // + the totals and the level-0 digest cells
   // Co-residency guard. The fused exchange waits inside k_eval: every block polls the peers' epoch flags
   // (each published by block 0 of that rank's launch) and, under node ownership, the owner's record of
   // the SAME block index -- waits on lower-or-equal block indices of the peers' launches, which in-order
   // dispatch starts first, so progress does not need a whole grid resident. The launch is still kept to
   // what this rank's CUs hold at once (occupancy x the CUs of its stream, COBALT_CU_BUDGET on a CU-masked
   // share of a shared device): a deeper level's grid than that runs the separate exchange kernel instead.
-  int resident = 0;
-  if (ipc) {
+  if (p.ipc) {
     int per_cu = 0;
-    const void* kf = eval_fg > 0 ? (const void*)k_eval<true, true, true> : (const void*)k_eval<false, true, true>;
-    const int threads = eval_fg > 0 ? ceil_div(eval_fg, 2) * kWave : 1024;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kf, threads, fused_lds) == hipSuccess)
-      resident = per_cu * device_cu_count();
+    const int threads = p.eval_fg > 0 ? ceil_div(p.eval_fg, 2) * kWave : 1024;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)eval_kernel(p.eval_fg > 0, true, true), threads,
+                                                     p.fused_lds) == hipSuccess)
+      p.resident = per_cu * device_cu_count();
   }
-  const int deepest_grid = (1 << (D - 1)) * (eval_fg > 0 ? ceil_div(d.F, eval_fg) : 1);
-  const bool ipc_fused = ipc && env_ipc_fused != 0 && fused_lds <= 65536 && resident >= deepest_grid;
-  d.ipc_epoch = 0;
-  d.ipcv = ipc_fused ? ipc_device_views(cc) : nullptr;
+  const int deepest_grid = (1 << (D - 1)) * (p.eval_fg > 0 ? ceil_div(d.F, p.eval_fg) : 1);
+  p.ipc_fused = p.ipc && env_ipc_fused != 0 && p.fused_lds <= 65536 && p.resident >= deepest_grid;
   // Split evaluation fused into the partition pass (k_eval_part): one launch per level fewer.
   //  * While a level's items fit one 1024-thread block per CU, every partition block evaluates its node
   //    itself (modes 0 / 1; 1M rows: 248.0 -> 239.3 us per tree in the stamps). Under data parallelism
@@ -3824,9 +3690,9 @@ static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool s
   static const int env_eb = knob_int(Knob::EvalBlocks, 1);
   const int ep_steps = ceil_div(chunk_part(d), 16 * kWave);
   bool eb_ok = env_eb != 0;  // (over the fused exchange: a CU holds the kernel with the exchange's LDS)
-  if (ipc_fused && eb_ok) {
+  if (p.ipc_fused && eb_ok) {
     int per_cu = 0;
-    eb_ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_eval_part<8, 2>, 1024, fused_lds) ==
+    eb_ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_eval_part<8, 2>, 1024, p.fused_lds) ==
                 hipSuccess && per_cu >= 1;
   }
   // node ownership (see node_owner): over the fused exchange (k_eval, or k_eval_part's evaluator blocks),
@@ -3834,53 +3700,29 @@ static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool s
   // the copy costs the other ranks one more remote round trip, not worth it for a level's few nodes),
   // and never before a level with a node per rank. COBALT_DP_OWNER=0: every rank evaluates every node
   static const int env_owner = knob_int(Knob::DpOwner, 1);
-  d.own_level = -1;
-  if (ipc_fused && env_owner && d.world > 1 && eval_fg == 0 && c->max_nodes <= kIpcDecNodes) {
+  p.own_level = -1;
+  if (p.ipc_fused && env_owner && d.world > 1 && p.eval_fg == 0 && c->max_nodes <= kIpcDecNodes) {
     int l0 = 0;
     while ((1 << l0) < d.world) ++l0;
     l0 = std::max(l0, D - 3);
-    d.own_level = l0 < D ? l0 : -1;
+    p.own_level = l0 < D ? l0 : -1;
   }
   // monotone / interaction constraints: one GPU, and the constrained evaluation is a kernel of its own
   // (k_eval_mono), so no fused evaluation + partition pass (as COBALT_EVAL_PART=0)
-  const bool mono = c->mono_on || c->inter_on;
-  if (mono && (dp || sampled)) return -16;
-  const bool eval_part = !mono && env_ep != 0 && (!ipc_fused || eb_ok) && eval_fg == 0 && ep_steps <= 8 && d.F <= 32;
-  // A level's fused pass: {item rows (0: separate k_eval + k_partition), mode}. Every-block form: the
-  // smallest item (1024-row steps from 4096) whose grid -- items + one partial item per node -- is one
-  // block per CU (a second round of blocks doubles the level; 1.25M rows: 6144 at every level).
+  p.mono = c->mono_on || c->inter_on;
+  if (p.mono && (p.dp || sampled)) return -16;
+  p.eval_part = !p.mono && env_ep != 0 && (!p.ipc_fused || eb_ok) && p.eval_fg == 0 && ep_steps <= 8 && d.F <= 32;
+  // Every-block form: the smallest item (1024-row steps from 4096) whose grid -- items + one partial item per
+  // node -- is one block per CU (a second round of blocks doubles the level; 1.25M rows: 6144 at every level).
   // Evaluator-block form: the same rule with one more block per node while it fits, else chunk_part.
-  auto ep_plan = [&](int level, int& mode) -> int {
-    mode = 0;
-    if (!eval_part || level + 1 >= D) return 0;
-    const int cus = device_cu_count();
-    const int extra = (ipc_fused ? 2 : 1) << level;
-    for (int ch = std::min(4096, chunk_part(d)); ch <= 8192; ch += 1024)
-      if (ceil_div(d.n, ch) + extra <= cus) {
-        mode = ipc_fused ? 2 : (dp ? 1 : 0);
-        return ch;
-      }
-    if (ipc_fused) { mode = 2; return chunk_part(d); }
-    return (env_ep == 2 && !dp) ? 8192 : 0;
-  };
-  c->plan[0] = ipc_fused ? 1 : 0;
-  c->plan[1] = d.own_level;
-  c->plan[2] = d.wide;
-  c->plan[3] = resident;
-  c->plan[4] = 0;  // levels run by the fused evaluation + partition pass (bit mask)
-  c->plan[5] = 0;  // ... of them in the evaluator-block form
-  c->plan[6] = 0;  // ... of those, levels whose grid (evaluators + items) exceeds one block per CU: the items
-                   // past the resident ones start as earlier blocks retire (in-order dispatch, evaluators first)
-  for (int level = 0; level + 1 < D; ++level) {
-    int m = 0;
-    const int ch = ep_plan(level, m);
-    if (ch > 0) {
-      c->plan[4] |= 1 << level;
-      if (m >= 2) c->plan[5] |= 1 << level;
-      if (m >= 2 && ceil_div(d.n, ch) + (2 << level) > device_cu_count()) c->plan[6] |= 1 << level;
-    }
+  for (int level = 0; p.eval_part && level + 1 < D; ++level) {
+    const int extra = (p.ipc_fused ? 2 : 1) << level;
+    int ch = std::min(4096, chunk_part(d));
+    while (ch <= 8192 && ceil_div(d.n, ch) + extra > device_cu_count()) ch += 1024;
+    if (ch <= 8192) p.ep[level] = {ch, p.ipc_fused ? 2 : (p.dp ? 1 : 0)};
+    else if (p.ipc_fused) p.ep[level] = {chunk_part(d), 2};
+    else p.ep[level] = {(env_ep == 2 && !p.dp) ? 8192 : 0, 0};
   }
-  d.zero_red = nullptr;
   // root items of the fused pass: <= 8192 rows (more blocks in flight than the 16384-row k_hist items);
   // COBALT_ROOT_CHUNK overrides (tuning experiments; multiple of 64 in [1024, 16384])
   static const int env_root = knob_int(Knob::RootChunk, 0);
@@ -3890,159 +3732,201 @@ static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool s
   // 2 blocks per CU: 8192-row items = 2.4 rounds, 9792-row items = 2 rounds: 167.5 -> 158.3 us per tree in
   // the stamps). Resident blocks per CU: 2 for the generic instantiation (~100 VGPRs x 512 threads), for a
   // record mode what the runtime reported for the kernel that will run with its LDS (set_layout; 3 on MI355X).
-  const int rmode = fuse_root ? root_mode(d, ft4) : -1;
-  const GradHistKernel root_k = fuse_root ? root_kernel(d, ft4, rmode) : nullptr;
-  const int root_per_cu = rmode > kRootGeneric ? c->root_rec_per_cu[rmode - 1] : 2;
-  if (fuse_root && (!root_k || root_per_cu < 1)) return -19;
-  c->plan[7] = rmode;
-  c->plan[8] = fuse_root ? root_per_cu : 0;
+  p.root_mode = p.fuse_root ? root_mode(d, p.ft4, p.mrec, p.dp) : -1;
+  p.root_kernel = p.fuse_root ? root_kernel(d, p.ft4, p.root_mode) : nullptr;
+  p.root_per_cu = !p.fuse_root ? 0 : p.root_mode > kRootGeneric ? c->root_rec_per_cu[p.root_mode - 1] : 2;
+  if (p.fuse_root && (!p.root_kernel || p.root_per_cu < 1)) return -19;
   int root_rule = std::min(chunk_hist(d, 0), 8192);
-  if (fuse_root) {
-    const int64_t res = (int64_t)root_per_cu * device_cu_count();
+  if (p.fuse_root) {
+    const int64_t res = (int64_t)p.root_per_cu * device_cu_count();
     const int64_t rounds = std::max<int64_t>(1, (d.n + res * 4096) / (res * 8192));  // nearest to n / (res * 8192)
     root_rule = (int)std::min<int64_t>(16384, std::max<int64_t>(1024, (ceil_div(d.n, rounds * res) + 63) / 64 * 64));
   }
-  const int root_chunk = std::max(root_min, env_root > 0 ? std::min(16384, std::max(1024, env_root / 64 * 64))
-                                                         : root_rule);
-  // COBALT_PART_POS=0: node-ordered partition items (k_partition) instead of position-ordered blocks
-  const bool part_pos = knob_int(Knob::PartPos, 1) != 0;
-  // Per tree: grad (+ root histogram, node-table init, archive/apply of the previous tree), then per
-  // level: hist -> reduce -> [data parallel: the histogram collective] -> eval [-> partition], or
-  // hist -> reduce [-> collective] -> the fused evaluation + partition pass; the last split level's
-  // children are finalised by its evaluation.
-  for (int t = t0; t < t0 + n_trees; ++t) {
-    if (t >= c->cfg.max_trees) return -10;
-    d.nodes = d.nodes_buf[t & 1];
-    d.prev_nodes = d.nodes_buf[(t + 1) & 1];
-    d.dig_slot = t & 1;
-    d.dig_check = t > c->fit_first ? 1 : 0;
-    d.corrupt = t == c->fault_tree ? 1 : 0;
-    d.stamps = stamp_tree(c, t) ? c->stamp_buf : nullptr;
-    const int apply = (t >= 1 && c->applied == t - 1) ? t - 1 : -1;  // prediction-cache update
-    // the root pass zeroes the root's reduce destination (under the fused exchange: the next send slot)
-    d.zero_red = ipc_fused ? static_cast<int64_t*>(ipc_send_buffer(cc)) : nullptr;
-    if (sampled)
-      GLAUNCH("k_tree_begin", k_tree_begin, dim3(std::max(1, std::min(64, ceil_div(d.slot_elems / 2, 256)))), dim3(256), 0,
-              stream, d);
-    else if (fuse_root)
-      GLAUNCH("k_grad_hist", root_k, dim3(ceil_div(d.n, root_chunk)), dim3(d.wide ? 1024 : 512), c->lds_hist + walk_lds,
-              stream, d, t, apply, root_chunk);
-    else
-      GLAUNCH("k_grad", k_grad, dim3(std::max(grad_grid, 1)), dim3(256), tree_lds, stream, d, t, apply);
-    if (apply >= 0 && !sampled) c->applied = t;
-    CK_LAUNCH();
-    for (int level = 0; level < D; ++level) {
-      const int parity = level & 1;
-      // this level's evaluation runs in the partition pass (k_eval_part) with items of ep_ch rows
-      int ep_mode = 0;
-      const int ep_ch = ep_plan(level, ep_mode);
-      const bool ep_level = ep_ch > 0;
-      d.ep_chunk = ep_ch;
-      d.ep_zero = dp ? 1 : 0;
-      const int slots = level == 0 ? 1 : (1 << (level - 1));
-      const int chh = (level == 0 && fuse_root) ? root_chunk : chunk_hist(d, level);
-      // with the row-count rule every pair builds its smaller child (<= half the parent's rows), so the
-      // level's items number at most ceil(n / 2 / chunk) + one partial item per pair: half the grid
-      // (and half the reduce grid) of the all-rows bound, fewer blocks that only plan and exit. The
-      // hessian rule (data parallel) may build the larger child: all-rows bound.
-      const int ub = (level > 0 && !d.by_hess) ? ceil_div((d.n + 1) / 2, chh) + (1 << (level - 1)) + 1
-                                               : ceil_div(d.n, chh) + (1 << level);
-      if (!(level == 0 && fuse_root))  // the fused gradient kernel already built the root histogram
-        GLAUNCH("k_hist", hist_kernel(ft4, d.hist_pair != 0, d.wide != 0), dim3(ub, ftiles), dim3(d.wide ? kHistThreadsWide : kHistThreads), c->lds_hist,
-                stream, d, parity, t, level, chh);
-      d.hist_red = ipc ? static_cast<int64_t*>(ipc_send_buffer(cc)) : nullptr;
-      const dim3 rgrid(ceil_div(ub, kRedItems), ceil_div((int64_t)d.ncells + 1, 256));
-      const int rn = std::min(ub, c->items_cap);
-      // (the row-count bound of the items, for the reduce blocks past it under the hessian rule)
-      const int likely = (level > 0 && d.by_hess) ? ceil_div((d.n + 1) / 2, chh) + (1 << (level - 1)) + 1 : rn;
-      if (dp)
-        GLAUNCH("k_hist_reduce", k_hist_reduce<true>, rgrid, dim3(256), 0, stream, d, parity, rn, level, likely);
-      else
-        GLAUNCH("k_hist_reduce", k_hist_reduce<false>, rgrid, dim3(256), 0, stream, d, parity, rn, level, likely);
-      CK_LAUNCH();
-      if (dp) {  // every rank built the globally chosen child (hessian rule): all-reduced as is
-        int rc;
-        // level 0 carries the replica-digest cell after the root slot (see GbdtDev::dig)
-        const int64_t count = (int64_t)slots * d.slot_elems + (level == 0 ? 2 : 0);
-        if (ipc_fused) {  // k_eval exchanges this epoch itself
-          d.ipc_epoch = ipc_next_epoch(cc);
-          rc = 0;
-        } else if (ipc) {  // the exchange also zeroes the next level's send slot (next tree's root after the last)
-          const int64_t next_slots = level + 1 < D ? (1 << level) : 1;
-          rc = ipc_exchange(cc, d.hist_b[parity], count, 0, 0, next_slots * d.slot_elems * (int64_t)sizeof(int64_t),
-                            stream);
-        } else {
-          rc = cobalt_comm_allreduce_sum_i64(c->cfg.comm, d.hist_b[parity], count, stream);
-        }
-        if (rc) return rc;
-      }
-      if (ep_level) {
-      } else if (eval_fg > 0) {  // features in groups of eval_fg over several CUs, then a per-node reduction
-        const int ng = ceil_div(d.F, eval_fg);
-        const dim3 eg(1 << level, ng), eb(ceil_div(eval_fg, 2) * kWave);
-        if (mono)
-          CONS_EVAL(true, eg, eb, 0, stream, d, level, parity, t, eval_fg, EvalSlots{}, c->cons);
-        else if (d.ipc_epoch)
-          GLAUNCH("k_eval", (k_eval<true, true, true>), eg, eb, fused_lds, stream, d, level, parity, t, eval_fg, EvalSlots{});
-        else if (dp)
-          GLAUNCH("k_eval", (k_eval<true, false, true>), eg, eb, 0, stream, d, level, parity, t, eval_fg, EvalSlots{});
-        else
-          GLAUNCH("k_eval", (k_eval<true, false, false>), eg, eb, 0, stream, d, level, parity, t, eval_fg, EvalSlots{});
-        if (mono)
-          CONS_FINISH(dim3(1 << level), dim3(kWave), 0, stream, d, level, parity, ng, c->cons);
-        else if (dp)
-          GLAUNCH("k_eval_finish", k_eval_finish<true>, dim3(1 << level), dim3(kWave), 0, stream, d, level, parity, ng);
-        else
-          GLAUNCH("k_eval_finish", k_eval_finish<false>, dim3(1 << level), dim3(kWave), 0, stream, d, level, parity, ng);
-      } else {
-        if (mono)
-          CONS_EVAL(false, dim3(1 << level), dim3(1024), 0, stream, d, level, parity, t, d.F, c->eval_slots, c->cons);
-        else if (d.ipc_epoch)
-          GLAUNCH("k_eval", (k_eval<false, true, true>), dim3(1 << level), dim3(1024), fused_lds, stream, d, level, parity,
-                  t, d.F, c->eval_slots);
-        else if (dp)
-          GLAUNCH("k_eval", (k_eval<false, false, true>), dim3(1 << level), dim3(1024), 0, stream, d, level, parity, t,
-                  d.F, c->eval_slots);
-        else
-          GLAUNCH("k_eval", (k_eval<false, false, false>), dim3(1 << level), dim3(1024), 0, stream, d, level, parity, t,
-                  d.F, c->eval_slots);
-      }
-      if (level + 1 < D) {  // the last split level's children are leaves: no row lists needed
-        const int chp = ep_level ? ep_ch : chunk_part(d);
-        const int ubp = ceil_div(d.n, chp) + (1 << level);
-        // (under the separate IPC exchange it overwrites the next level's hist_b slots whole: nothing to
-        // zero; under the fused one the next level's send slot is the reduce destination to zero)
-        const int64_t zero_next = (ipc && !ipc_fused) ? 0 : (int64_t)(1 << level) * d.slot_elems;
-        d.zero_red = ipc_fused ? static_cast<int64_t*>(ipc_send_buffer(cc)) : nullptr;
-        const int steps = ceil_div(chp, 16 * kWave);  // <= 8 (chunk_part's cap)
-        if (ep_level) {
-          c->d.seq = stamp_next(c, "k_eval_part");
-          const int evals = ep_mode >= 2 ? (1 << level) : 0;  // the evaluator blocks come first
-          launch_eval_part(steps, ep_mode, dim3(ubp + evals), ep_mode == 2 ? fused_lds : 0, stream, d, parity, zero_next,
-                           level, chp, t, c->eval_slots, ++c->dec_tag);
-        } else if (part_pos && (1 << level) <= kPartPosNodes) {  // position-ordered blocks (k_part_pos)
-          // (the grid from the instantiation's rows per block: COBALT_PART_CHUNK may give 1-3 or 5-7 steps)
-          const int ps = steps <= 4 ? 4 : 8;
-          const dim3 pg(std::max(1, (int)ceil_div(d.n, (int64_t)16 * kWave * ps)));
-          if (ps == 4)
-            GLAUNCH("k_partition", (k_part_pos<4>), pg, dim3(16 * kWave), 0, stream, d, parity, zero_next, level);
-          else
-            GLAUNCH("k_partition", (k_part_pos<8>), pg, dim3(16 * kWave), 0, stream, d, parity, zero_next, level);
-        } else if (steps <= 4)
-          GLAUNCH("k_partition", (k_partition<16, 4>), dim3(ubp), dim3(16 * kWave), 0, stream, d, parity, zero_next,
-                  level, chp);
-        else
-          GLAUNCH("k_partition", (k_partition<16, 8>), dim3(ubp), dim3(16 * kWave), 0, stream, d, parity, zero_next,
-                  level, chp);
-      }
-      d.ipc_epoch = 0;
-      CK_LAUNCH();
-    }
-    c->grown = t + 1;
-    if (sampled) c->applied = t + 1;  // no training margins on a per-tree sample
-    d.zero_red = nullptr;
+  p.root_chunk = std::max(root_min, env_root > 0 ? std::min(16384, std::max(1024, env_root / 64 * 64)) : root_rule);
+  p.part_pos = knob_int(Knob::PartPos, 1) != 0;
+  *out = p;
+  return 0;
+}
+
+// The plan as cobalt_gbdt_plan exports it (PlanIdx).
+static void export_plan(GbdtCtx* c, const GrowPlan& p) {
+  const GbdtDev& d = c->d;
+  int32_t* e = c->plan;
+  e[kPlanIpcFused] = p.ipc_fused ? 1 : 0;
+  e[kPlanOwnLevel] = p.own_level;
+  e[kPlanWide] = d.wide;
+  e[kPlanResident] = p.resident;
+  e[kPlanEpLevels] = e[kPlanEbLevels] = e[kPlanEbOverflow] = 0;
+  for (int level = 0; level + 1 < d.max_depth; ++level) {
+    const int ch = p.ep[level].chunk, m = p.ep[level].mode;
+    if (ch <= 0) continue;
+    e[kPlanEpLevels] |= 1 << level;
+    if (m >= 2) e[kPlanEbLevels] |= 1 << level;
+    // the items past the resident ones start as earlier blocks retire (in-order dispatch, evaluators first)
+    if (m >= 2 && ceil_div(d.n, ch) + (2 << level) > device_cu_count()) e[kPlanEbOverflow] |= 1 << level;
   }
-  // archive the last tree of this call (later trees are archived by the next tree's k_grad)
+  e[kPlanRootMode] = p.root_mode;
+  e[kPlanRootPerCu] = p.root_per_cu;
+}
+
+// One level of tree t: hist -> reduce -> [data parallel: the histogram collective] -> eval [-> partition], or
+// hist -> reduce [-> collective] -> the fused evaluation + partition pass; the last split level's children are
+// finalised by its evaluation.
+static int enqueue_level(GbdtCtx* c, const GrowPlan& p, int t, int level, hipStream_t stream) {
+  GbdtDev& d = c->d;
+  const int D = d.max_depth;
+  CobaltComm* const cc = static_cast<CobaltComm*>(c->cfg.comm);
+  const int parity = level & 1;
+  // this level's evaluation runs in the partition pass (k_eval_part) with items of ep_ch rows
+  const int ep_ch = p.ep[level].chunk, ep_mode = p.ep[level].mode;
+  const bool ep_level = ep_ch > 0;
+  d.ep_chunk = ep_ch;
+  d.ep_zero = p.dp ? 1 : 0;
+  const int slots = level == 0 ? 1 : (1 << (level - 1));
+  const int chh = (level == 0 && p.fuse_root) ? p.root_chunk : chunk_hist(d, level);
+  // with the row-count rule every pair builds its smaller child (<= half the parent's rows), so the
+  // level's items number at most ceil(n / 2 / chunk) + one partial item per pair: half the grid
+  // (and half the reduce grid) of the all-rows bound, fewer blocks that only plan and exit. The
+  // hessian rule (data parallel) may build the larger child: all-rows bound.
+  const int ub = (level > 0 && !d.by_hess) ? ceil_div((d.n + 1) / 2, chh) + (1 << (level - 1)) + 1
+                                           : ceil_div(d.n, chh) + (1 << level);
+  if (!(level == 0 && p.fuse_root))  // the fused gradient kernel already built the root histogram
+    GLAUNCH("k_hist", hist_kernel(p.ft4, d.hist_pair != 0, d.wide != 0), dim3(ub, p.ftiles),
+            dim3(d.wide ? kHistThreadsWide : kHistThreads), c->lds_hist, stream, d, parity, t, level, chh);
+  d.hist_red = p.ipc ? static_cast<int64_t*>(ipc_send_buffer(cc)) : nullptr;
+  const dim3 rgrid(ceil_div(ub, kRedItems), ceil_div((int64_t)d.ncells + 1, 256));
+  const int rn = std::min(ub, c->items_cap);
+  // (the row-count bound of the items, for the reduce blocks past it under the hessian rule)
+  const int likely = (level > 0 && d.by_hess) ? ceil_div((d.n + 1) / 2, chh) + (1 << (level - 1)) + 1 : rn;
+  if (p.dp)
+    GLAUNCH("k_hist_reduce", k_hist_reduce<true>, rgrid, dim3(256), 0, stream, d, parity, rn, level, likely);
+  else
+    GLAUNCH("k_hist_reduce", k_hist_reduce<false>, rgrid, dim3(256), 0, stream, d, parity, rn, level, likely);
+  CK_LAUNCH();
+  if (p.dp) {  // every rank built the globally chosen child (hessian rule): all-reduced as is
+    int rc;
+    // level 0 carries the replica-digest cell after the root slot (see GbdtDev::dig)
+    const int64_t count = (int64_t)slots * d.slot_elems + (level == 0 ? 2 : 0);
+    if (p.ipc_fused) {  // k_eval exchanges this epoch itself
+      d.ipc_epoch = ipc_next_epoch(cc);
+      rc = 0;
+    } else if (p.ipc) {  // the exchange also zeroes the next level's send slot (next tree's root after the last)
+      const int64_t next_slots = level + 1 < D ? (1 << level) : 1;
+      rc = ipc_exchange(cc, d.hist_b[parity], count, 0, 0, next_slots * d.slot_elems * (int64_t)sizeof(int64_t), stream);
+    } else {
+      rc = cobalt_comm_allreduce_sum_i64(c->cfg.comm, d.hist_b[parity], count, stream);
+    }
+    if (rc) return rc;
+  }
+  if (ep_level) {
+  } else if (p.eval_fg > 0) {  // features in groups of eval_fg over several CUs, then a per-node reduction
+    const int ng = ceil_div(d.F, p.eval_fg);
+    const dim3 eg(1 << level, ng), eb(ceil_div(p.eval_fg, 2) * kWave);
+    launch_eval(c, true, eg, eb, p.fused_lds, stream, level, parity, t, p.eval_fg, EvalSlots{});
+    launch_eval_finish(c, stream, level, parity, ng);
+  } else {
+    launch_eval(c, false, dim3(1 << level), dim3(1024), p.fused_lds, stream, level, parity, t, d.F, c->eval_slots);
+  }
+  if (level + 1 < D) {  // the last split level's children are leaves: no row lists needed
+    const int chp = ep_level ? ep_ch : chunk_part(d);
+    const int ubp = ceil_div(d.n, chp) + (1 << level);
+    // (under the separate IPC exchange it overwrites the next level's hist_b slots whole: nothing to
+    // zero; under the fused one the next level's send slot is the reduce destination to zero)
+    const int64_t zero_next = (p.ipc && !p.ipc_fused) ? 0 : (int64_t)(1 << level) * d.slot_elems;
+    d.zero_red = p.ipc_fused ? static_cast<int64_t*>(ipc_send_buffer(cc)) : nullptr;
+    const int steps = ceil_div(chp, 16 * kWave);  // <= 8 (chunk_part's cap)
+    if (ep_level) {
+      c->d.seq = stamp_next(c, "k_eval_part");
+      const int evals = ep_mode >= 2 ? (1 << level) : 0;  // the evaluator blocks come first
+      launch_eval_part(steps, ep_mode, dim3(ubp + evals), ep_mode == 2 ? p.fused_lds : 0, stream, d, parity, zero_next,
+                       level, chp, t, c->eval_slots, ++c->dec_tag);
+    } else if (p.part_pos && (1 << level) <= kPartPosNodes) {  // position-ordered blocks (k_part_pos)
+      // (the grid from the instantiation's rows per block: COBALT_PART_CHUNK may give 1-3 or 5-7 steps)
+      const int ps = steps <= 4 ? 4 : 8;
+      const dim3 pg(std::max(1, (int)ceil_div(d.n, (int64_t)16 * kWave * ps)));
+      if (ps == 4)
+        GLAUNCH("k_partition", (k_part_pos<4>), pg, dim3(16 * kWave), 0, stream, d, parity, zero_next, level);
+      else
+        GLAUNCH("k_partition", (k_part_pos<8>), pg, dim3(16 * kWave), 0, stream, d, parity, zero_next, level);
+    } else if (steps <= 4)
+      GLAUNCH("k_partition", (k_partition<16, 4>), dim3(ubp), dim3(16 * kWave), 0, stream, d, parity, zero_next, level,
+              chp);
+    else
+      GLAUNCH("k_partition", (k_partition<16, 8>), dim3(ubp), dim3(16 * kWave), 0, stream, d, parity, zero_next, level,
+              chp);
+  }
+  d.ipc_epoch = 0;
+  CK_LAUNCH();
+  return 0;
+}
+
+// Tree t: grad (+ root histogram, node-table init, archive/apply of the previous tree), then its levels.
+static int enqueue_tree(GbdtCtx* c, const GrowPlan& p, int t, hipStream_t stream) {
+  GbdtDev& d = c->d;
+  if (t >= c->cfg.max_trees) return -10;
+  d.nodes = d.nodes_buf[t & 1];
+  d.prev_nodes = d.nodes_buf[(t + 1) & 1];
+  d.dig_slot = t & 1;
+  d.dig_check = t > c->fit_first ? 1 : 0;
+  d.corrupt = t == c->fault_tree ? 1 : 0;
+  d.stamps = stamp_tree(c, t) ? c->stamp_buf : nullptr;
+  const int apply = (t >= 1 && c->applied == t - 1) ? t - 1 : -1;  // prediction-cache update
+  // the root pass zeroes the root's reduce destination (under the fused exchange: the next send slot)
+  d.zero_red = p.ipc_fused ? static_cast<int64_t*>(ipc_send_buffer(static_cast<CobaltComm*>(c->cfg.comm))) : nullptr;
+  if (p.sampled)
+    GLAUNCH("k_tree_begin", k_tree_begin, dim3(std::max(1, std::min(64, ceil_div(d.slot_elems / 2, 256)))), dim3(256), 0,
+            stream, d);
+  else if (p.fuse_root)
+    GLAUNCH("k_grad_hist", p.root_kernel, dim3(ceil_div(d.n, p.root_chunk)), dim3(d.wide ? 1024 : 512),
+            c->lds_hist + p.walk_lds, stream, d, t, apply, p.root_chunk);
+  else
+    GLAUNCH("k_grad", k_grad, dim3(std::max(p.grad_grid, 1)), dim3(256), p.tree_lds, stream, d, t, apply);
+  if (apply >= 0 && !p.sampled) c->applied = t;
+  CK_LAUNCH();
+  for (int level = 0; level < d.max_depth; ++level)
+    if (int rc = enqueue_level(c, p, t, level, stream)) return rc;
+  c->grown = t + 1;
+  if (p.sampled) c->applied = t + 1;  // no training margins on a per-tree sample
+  d.zero_red = nullptr;
+  return 0;
+}
+
+// Enqueue `n_trees` boosting rounds starting at tree index `t0`. No host synchronisation.
+// `sampled`: the row records already hold the (reweighted) gradient pairs of this tree's rows --
+// the external-memory path, where k_ooc_page wrote a fresh sample -- so the tree starts with a
+// node-table reset + a plain root histogram instead of the gradient pass, and no margins are kept.
+static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool sampled) {
+  GrowPlan p;
+  if (int rc = plan_grow(c, t0, sampled, &p)) return rc;  // (nothing enqueued, label_pending kept)
+  export_plan(c, p);
+  GbdtDev& d = c->d;
+  CobaltComm* const cc = static_cast<CobaltComm*>(c->cfg.comm);
+  // the GbdtDev fields the plan determines
+  d.dp = p.dp ? 1 : 0;
+  d.mrec = p.mrec ? 1 : 0;
+  d.own_level = p.own_level;
+  d.ipc_epoch = 0;
+  d.ipcv = p.ipc_fused ? ipc_device_views(cc) : nullptr;
+  d.hist_red = nullptr;
+  d.zero_red = nullptr;
+  // prologue: stamps, the first send slot, the labels / margins into the records
+  if (int rc = stamp_begin(c, stream)) return rc;
+  if (p.ipc)
+    if (int rc = ipc_zero_send(cc, d.slot_elems * (int64_t)sizeof(int64_t), stream)) return rc;
+  if (c->label_pending || p.mrec) {
+    const dim3 g1(std::max(1, std::min(ceil_div(d.n, 256), 4096)));
+    if (c->label_pending && p.mrec)
+      hipLaunchKernelGGL(k_margin_label_in, g1, dim3(256), 0, stream, d.bins, d.margin, d.label, d.n);
+    else if (c->label_pending)
+      hipLaunchKernelGGL(k_put_label31, g1, dim3(256), 0, stream, d.bins, d.label, d.n);
+    else
+      hipLaunchKernelGGL(k_margin_in, g1, dim3(256), 0, stream, d.bins, d.margin, d.n);
+    CK_LAUNCH();
+  }
+  c->label_pending = false;
+  for (int t = t0; t < t0 + n_trees; ++t)
+    if (int rc = enqueue_tree(c, p, t, stream)) return rc;
+  // epilogue: archive the last tree of this call (later trees are archived by the next tree's k_grad)
   if (c->grown > t0) {
     const int last = c->grown - 1;
     CK(hipMemcpyAsync(d.trees + (size_t)last * c->max_nodes, d.nodes_buf[last & 1], c->max_nodes * sizeof(Node),
@@ -4056,12 +3940,12 @@ static int grow_impl(GbdtCtx* c, int t0, int n_trees, hipStream_t stream, bool s
   }
   // bring the margins up to date with the last grown tree
   if (c->applied < c->grown) {
-    GLAUNCH("k_apply_tree", k_apply_tree, dim3(std::max(grad_grid, 1)), dim3(256), tree_lds, stream, d, c->grown - 1);
+    GLAUNCH("k_apply_tree", k_apply_tree, dim3(std::max(p.grad_grid, 1)), dim3(256), p.tree_lds, stream, d, c->grown - 1);
     CK_LAUNCH();
     c->applied = c->grown;
   }
   // the last tree of the call: its replica digest checked by a collective of its own (see k_dig_stage)
-  if (dp && c->grown > t0) {
+  if (p.dp && c->grown > t0) {
     const int ls = (c->grown - 1) & 1;
     hipLaunchKernelGGL(k_dig_stage, dim3(1), dim3(64), 0, stream, d.dig, ls);
     CK_LAUNCH();
@@ -4318,254 +4202,7 @@ COBALT_API int cobalt_gbdt_unpermute(void* h, hipStream_t stream) {
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------
-// Exact external-memory training (histograms over page-resident chunks, the analog of
-// XGBoost's external-memory `hist` without sampling). The quantised pages stay in host DRAM (or HBM
-// under a budget); on the device every row keeps only its margin, label, weight, packed (g, h) and its
-// current node (2 B): ~22 B per row instead of the in-core ~72 B. A tree is grown level by level, and
-// every level streams every page once:
-//   * level -1 (k_ox_page, mode grad): the previous tree's leaf (found through the row's node) is added
-//     to its margin, g / h are computed and quantised exactly as the in-core root pass does (same
-//     dither key: per tree and GLOBAL row), every row moves to the root, the root histogram is built;
-//   * level L >= 0: a row of a node split at level L moves to its child (the split feature's bin from
-//     the page), and a row entering the child the evaluation chose to build (smaller hessian) adds its
-//     (g, h) to that child pair's histogram;
-//   * after each pass: the per-block partial histograms are reduced into the in-core trainer's level
-//     slots (k_ox_reduce) and the in-core split evaluation (k_eval) runs on them unchanged -- same
-//     node table, same subtraction trick, same finalisation.
-// Every histogram is an exact integer sum, so the trees are byte-identical to the in-core fit of the
-// same rows (tests/test_external.py). Histograms: each block privatises the pair slots of its group
-// (gridDim.y groups) in LDS as packed u64 cells -- flushed to its own int64 slab rows every 16384 rows
-// (the packed halves cannot carry within that) -- so the page data is read once per slot group.
-// ------------------------------------------------------------------------------------------
-constexpr int kOxSlab = 128;           // blocks per page pass (= slab rows per pair slot)
-constexpr int kOxFlushRows = 16384;    // rows per LDS flush (packed u64 bound, as the in-core blocks)
-constexpr size_t kOxLdsBudget = 150 * 1024;
-
-static int ox_group_slots(const GbdtDev& d) {
-  return std::max<int>(1, (int)(kOxLdsBudget / ((size_t)(d.ncells + 1) * sizeof(uint64_t))));
-}
-
-// mode: -1 = gradient pass (+ root histogram), L >= 0 = route level L + histogram of level L + 1.
-__global__ __launch_bounds__(1024) void k_ox_page(GbdtDev d, const uint8_t* __restrict__ page, int ps, int64_t n,
-                                                  int64_t r0, int mode, int tree, int apply, uint16_t* __restrict__ pos,
-                                                  uint64_t* __restrict__ gh, int64_t* __restrict__ slab,
-                                                  float* __restrict__ margin, const float* __restrict__ label,
-                                                  const float* __restrict__ weight, int gslots) {
-  extern __shared__ uint64_t s_h[];  // [gslots][ncells + 1] packed (g, h); cell ncells = the slot's totals
-  __shared__ uint32_t s_meta[256];
-  __shared__ float s_leaf[256];
-  __shared__ uint8_t s_build[256];
-  __shared__ int s_hoff[kMaxFeatTile + 1];
-  __shared__ int s_nb[kMaxFeatTile];  // bin count, 0 for a feature colsample masked out of this tree
-  const int F = d.F, nc = d.ncells, cells = nc + 1;
-  const int g0 = blockIdx.y * gslots;                                  // first slot of this block's group
-  const int nslots = mode < 0 ? 1 : (1 << mode);                       // pairs of level mode + 1
-  const int gs = min(gslots, nslots - g0);
-  if (gs <= 0) return;
-  const Node* tab = (mode < 0) ? d.prev_nodes : d.nodes;              // tree staged for this pass
-  for (int i = threadIdx.x; i < d.max_nodes && i < 256; i += blockDim.x) {
-    const Node nd = tab[i];
-    s_meta[i] = node_meta(nd);
-    s_leaf[i] = nd.leaf_value;
-    s_build[i] = (uint8_t)(nd.build != 0);
-  }
-  for (int f = threadIdx.x; f <= F; f += blockDim.x) {
-    s_hoff[f] = d.hoff[f];
-    if (f < F) s_nb[f] = d.fmask[(int64_t)tree * F + f] ? d.nbins[f] : 0;
-  }
-  const uint64_t tree_key = tree_key_of(d.seed, tree);
-  const uint64_t dkey = splitmix64(tree_key ^ kDitherSalt);
-  const int first = mode < 0 ? 0 : (1 << mode) - 1;
-  const int64_t per = (n + gridDim.x - 1) / gridDim.x;
-  const int64_t b0 = min(n, (int64_t)blockIdx.x * per), b1 = min(n, b0 + per);
-  int64_t* my = slab + (int64_t)blockIdx.x * d.slot_elems * (int64_t)(1 << (d.max_depth - 1));
-  for (int64_t c0 = b0; c0 < b1; c0 += kOxFlushRows) {
-    const int64_t c1 = min(b1, c0 + kOxFlushRows);
-    __syncthreads();  // (previous flush done with s_h; staged tables visible)
-    for (int i = threadIdx.x; i < gs * cells; i += blockDim.x) s_h[i] = 0ull;
-    __syncthreads();
-    for (int64_t i = c0 + threadIdx.x; i < c1; i += blockDim.x) {
-      const int64_t r = r0 + i;
-      const uint8_t* row = page + i * ps;
-      int slot = -1;
-      uint64_t v = 0;
-      if (mode < 0) {  // gradients (+ the previous tree's leaf), every row builds the root
-        float mf = margin[r];
-        if (apply) {  // the previous tree's leaf: from the row's last routed node down (its last level
-                      // was evaluated but not routed), with the page's bins
-          int nd = pos[r];
-          uint32_t m = s_meta[nd];
-          while (m & kMetaSplit) {
-            const uint32_t b = row[m & 0xFFFFu];
-            const bool left = meta_left(m, b);
-            nd = 2 * nd + (left ? 1 : 2);
-            m = s_meta[nd];
-          }
-          mf += s_leaf[nd];
-          margin[r] = mf;
-        }
-        const double p = 1.0 / (1.0 + exp(-(double)mf));
-        const double y = (double)label[r], w = (double)weight[r];
-        double g = (p - y) * w;
-        double h = fmax(p * (1.0 - p), 1e-16) * w;
-        if (d.subsample < 1.0) {
-          const uint64_t hsh = splitmix64(tree_key ^ (uint64_t)(d.row_offset + r));
-          if (!(uniform01(hsh) < d.subsample)) { g = 0.0; h = 0.0; }
-        }
-        int64_t gq, hq;
-        quantize_gh(g, h, d.gscale, d.hscale, dkey, d.row_offset + r, gq, hq);
-        v = ((uint64_t)(uint32_t)(int32_t)gq << 32) | (uint64_t)(uint32_t)hq;
-        gh[r] = v;
-        pos[r] = 0;
-        slot = 0;
-      } else {  // route a row of a split node of this level; it may build its child's pair histogram
-        // (with several slot groups the y = 0 blocks store the routed position; another group's block
-        // can read the row before or after that store, so a position already on level mode + 1 counts
-        // as routed from its parent)
-        int nd = pos[r];
-        int ch = -1;
-        if (nd >= 2 * first + 1) {
-          ch = nd;
-          nd = (nd - 1) >> 1;
-        } else if (nd >= first) {
-          const uint32_t m = s_meta[nd];
-          if (m & kMetaSplit) {
-            const uint32_t b = row[m & 0xFFFFu];
-            const bool left = meta_left(m, b);
-            ch = 2 * nd + (left ? 1 : 2);
-            if (blockIdx.y == 0) pos[r] = (uint16_t)ch;
-          }
-        }
-        if (ch >= 0 && s_build[ch]) {
-          slot = nd - first;
-          v = gh[r];
-        }
-      }
-      const int ls = slot - g0;
-      if (slot >= 0 && ls >= 0 && ls < gs) {
-        unsigned long long* hs = reinterpret_cast<unsigned long long*>(s_h + (int64_t)ls * cells);
-        atomicAdd(hs + nc, (unsigned long long)v);  // the slot's (G, H)
-        for (int f = 0; f < F; ++f) {
-          const int b = row[f];
-          if (b < s_nb[f]) atomicAdd(hs + s_hoff[f] + b, (unsigned long long)v);
-        }
-      }
-    }
-    __syncthreads();
-    // flush: this block owns its slab rows (no atomics); only non-zero cells are written
-    for (int i = threadIdx.x; i < gs * cells; i += blockDim.x) {
-      const uint64_t pv = s_h[i];
-      if (!pv) continue;
-      const int ls = i / cells, c = i - ls * cells;
-      int64_t* dst = my + (int64_t)(g0 + ls) * d.slot_elems + 2 * c;
-      dst[0] += (int64_t)(int32_t)(uint32_t)(pv >> 32);
-      dst[1] += (int64_t)(uint32_t)pv;
-    }
-  }
-}
-
-// Level histograms: the kOxSlab per-block slab rows of each pair slot summed into hist_b[parity] (the
-// in-core evaluation's input, totals cell included), the slab zeroed behind the read.
-__global__ __launch_bounds__(256) void k_ox_reduce(GbdtDev d, int64_t* __restrict__ slab, int parity, int slots) {
-  const int s = blockIdx.x;
-  const int64_t e = ((int64_t)blockIdx.y * blockDim.x + threadIdx.x) * 2;
-  if (e >= d.slot_elems || s >= slots) return;
-  const int64_t rowstride = d.slot_elems * (int64_t)(1 << (d.max_depth - 1));
-  int64_t g = 0, h = 0;
-  for (int b = 0; b < kOxSlab; ++b) {
-    int64_t* p = slab + b * rowstride + (int64_t)s * d.slot_elems + e;
-    g += p[0];
-    h += p[1];
-    p[0] = 0;
-    p[1] = 0;
-  }
-  int64_t* o = d.hist_b[parity] + (int64_t)s * d.slot_elems + e;
-  o[0] = g;
-  o[1] = h;
-}
-
-COBALT_API int cobalt_gbdt_ox_init(void* h, int64_t n, float* margin, const float* label, const float* weight) {
-  GbdtCtx* c = static_cast<GbdtCtx*>(h);
-  if (c->d.F > kMaxFeatTile || c->max_nodes > 256 || c->d.F > 32) return -15;  // depth <= 7, <= 32 features
-  if (c->d.wide) return -15;  // (the out-of-core passes accumulate 17-bit packed pairs)
-  if (c->ox_pos) return -16;
-  c->ox_n = n;
-  int rc;
-  if ((rc = dev_alloc(c, (void**)&c->ox_pos, (size_t)std::max<int64_t>(n, 1) * sizeof(uint16_t)))) return rc;
-  if ((rc = dev_alloc(c, (void**)&c->ox_gh, (size_t)std::max<int64_t>(n, 1) * sizeof(uint64_t)))) return rc;
-  const size_t sb = (size_t)kOxSlab * c->pairs_max * c->d.slot_elems * sizeof(int64_t);
-  if ((rc = dev_alloc(c, (void**)&c->ox_slab, sb))) return rc;
-  CK(hipMemset(c->ox_slab, 0, sb));
-  c->ox_margin = margin;
-  c->ox_label = label;
-  c->ox_weight = weight;
-  const size_t lds = (size_t)ox_group_slots(c->d) * (c->d.ncells + 1) * sizeof(uint64_t);
-  CK(hipFuncSetAttribute((const void*)k_ox_page, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return 0;
-}
-
-// Start tree t: node tables (the new one reset, the previous one kept for the margin update).
-COBALT_API int cobalt_gbdt_ox_begin(void* h, int t, hipStream_t stream) {
-  GbdtCtx* c = static_cast<GbdtCtx*>(h);
-  if (t != c->grown || t >= c->cfg.max_trees) return -11;
-  GbdtDev& d = c->d;
-  d.nodes = d.nodes_buf[t & 1];
-  d.prev_nodes = d.nodes_buf[(t + 1) & 1];
-  d.zero_red = nullptr;
-  d.stamps = nullptr;
-  hipLaunchKernelGGL(k_tree_begin, dim3(std::max(1, std::min(64, ceil_div(d.slot_elems / 2, 256)))), dim3(256), 0,
-                     stream, d);
-  CK_LAUNCH();
-  return 0;
-}
-
-// One page of the current pass (mode -1 = gradients, L = route level L). Rows r0 .. r0 + n of the data
-// set, `ps` bytes per row (the F bins first).
-COBALT_API int cobalt_gbdt_ox_page(void* h, const uint8_t* page, int ps, int64_t n, int64_t r0, int mode, int t,
-                                   hipStream_t stream) {
-  GbdtCtx* c = static_cast<GbdtCtx*>(h);
-  const GbdtDev& d = c->d;
-  if (!c->ox_pos || r0 < 0 || r0 + n > c->ox_n || ps < d.F || mode >= d.max_depth - 1) return -3;
-  if (n <= 0) return 0;
-  const int gsl = ox_group_slots(d);
-  const int nslots = mode < 0 ? 1 : (1 << mode);
-  const dim3 grid(kOxSlab, ceil_div(nslots, gsl));
-  const int gs = std::min(gsl, nslots);
-  const size_t lds = (size_t)gs * (d.ncells + 1) * sizeof(uint64_t);
-  const int apply = (mode < 0 && t > c->fit_first) ? 1 : 0;
-  hipLaunchKernelGGL(k_ox_page, grid, dim3(1024), lds, stream, d, page, ps, n, r0, mode, t, apply, c->ox_pos, c->ox_gh,
-                     c->ox_slab, c->ox_margin, c->ox_label, c->ox_weight, gsl);
-  CK_LAUNCH();
-  return 0;
-}
-
-// After the pass that built level `level`'s histograms: reduce them and evaluate the level.
-COBALT_API int cobalt_gbdt_ox_level(void* h, int level, int t, hipStream_t stream) {
-  GbdtCtx* c = static_cast<GbdtCtx*>(h);
-  GbdtDev& d = c->d;
-  if (level < 0 || level >= d.max_depth) return -3;
-  const int parity = level & 1;
-  const int slots = level == 0 ? 1 : (1 << (level - 1));
-  hipLaunchKernelGGL(k_ox_reduce, dim3(slots, ceil_div(d.slot_elems / 2, 256)), dim3(256), 0, stream, d, c->ox_slab,
-                     parity, slots);
-  CK_LAUNCH();
-  hipLaunchKernelGGL((k_eval<false, false, false>), dim3(1 << level), dim3(1024), 0, stream, d, level, parity, t, d.F,
-                     c->eval_slots);
-  CK_LAUNCH();
-  return 0;
-}
-
-// Finish tree t: archive its node table.
-COBALT_API int cobalt_gbdt_ox_end(void* h, int t, hipStream_t stream) {
-  GbdtCtx* c = static_cast<GbdtCtx*>(h);
-  GbdtDev& d = c->d;
-  CK(hipMemcpyAsync(d.trees + (size_t)t * c->max_nodes, d.nodes_buf[t & 1], c->max_nodes * sizeof(Node),
-                    hipMemcpyDeviceToDevice, stream));
-  c->grown = t + 1;
-  c->applied = t;
-  return 0;
-}
+#include "gbdt_ox.h"
 
 // External memory: grow tree t from the sample the last k_ooc_page passes wrote into the trainer's
 // row records / feature-major bins (n_rows set by cobalt_gbdt_set_rows).
@@ -4597,19 +4234,6 @@ COBALT_API int cobalt_gbdt_fetch_trees(void* h, int t0, int n, void* host_out, h
 }
 
 COBALT_API int cobalt_gbdt_max_nodes(void* h) { return static_cast<GbdtCtx*>(h)->max_nodes; }
-
-// Resume: the margins passed to set_data already contain trees [0, t0) (re-predicted from a
-// checkpoint); boosting continues at global tree index t0, so row sampling and column masks -- both
-// keyed by the global tree index -- follow the uninterrupted run exactly.
-// Binary labels into the row records (see GbdtDev::ylab): after set_data, for a fit whose labels are
-// all 0 or 1 and whose weights are 1 (negatives) or `spw` (positives) -- the caller checks both. Writes
-// byte 23 of every record (padding: bins occupy bytes 0..F-1, F <= 23 -- for F > 20 the histogram reads
-// byte 23 as a padding feature's bin, which goes to the trash cell -- and the gradient pass rewrites
-// bytes 16..31 from the record it read). Saves 8 of the ~80 bytes per row the gradient pass moves.
-__global__ __launch_bounds__(256) void k_put_label(uint8_t* bins, const float* label, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    bins[i * 32 + 23] = label[i] != 0.0f ? 1 : 0;
-}
 
 COBALT_API int cobalt_gbdt_set_binary_labels(void* h, float spw, hipStream_t stream) {
   GbdtCtx* c = static_cast<GbdtCtx*>(h);
@@ -4682,6 +4306,9 @@ COBALT_API int cobalt_gbdt_set_interaction(void* h, const uint64_t* fgroups, int
   return 0;
 }
 
+// Resume: the margins passed to set_data already contain trees [0, t0) (re-predicted from a
+// checkpoint); boosting continues at global tree index t0, so row sampling and column masks -- both
+// keyed by the global tree index -- follow the uninterrupted run exactly.
 COBALT_API int cobalt_gbdt_set_start(void* h, int t0) {
   GbdtCtx* c = static_cast<GbdtCtx*>(h);
   if (t0 < 0 || t0 > c->cfg.max_trees || c->grown != 0) return -12;
@@ -4694,10 +4321,13 @@ COBALT_API int cobalt_gbdt_set_start(void* h, int t0) {
 // The last grow call's launch plan (GbdtCtx::plan): out[0] fused IPC exchange, [1] node-ownership level
 // (-1 off), [2] wide gradients, [3] blocks of the fused k_eval this rank's CUs hold at once, [4] bit mask of
 // the levels run by the fused evaluation + partition pass, [5] of them in the evaluator-block form, [6] of
-// those the levels whose grid exceeds one block per CU.
+// those the levels whose grid exceeds one block per CU, [7] the fused root pass's data mode (kRootGeneric /
+// kRootRec / kRootRecOrig; -1: no fused root pass), [8] the resident blocks per CU its grid was sized for (0
+// without a fused root pass).
 COBALT_API int cobalt_gbdt_plan(void* h, int32_t* out) {
   GbdtCtx* c = static_cast<GbdtCtx*>(h);
-  for (int k = 0; k < 9; ++k) out[k] = c->plan[k];
+  static_assert(kPlanCount == 9, "ops/gbdt_ops.py reads nine entries");
+  for (int k = 0; k < kPlanCount; ++k) out[k] = c->plan[k];
   return 0;
 }
 
@@ -4763,93 +4393,6 @@ COBALT_API int cobalt_gbdt_destroy(void* h) {
   if (c->err_pinned) (void)hipHostFree(c->err_pinned);
   delete c;
   return 0;
-}
-
-// Quantise n rows into row records (pitch `stride`) and feature-major bins with row pitch `ldt`
-// (ldt = n for a whole matrix; the full row count when a streamed chunk is binned in place).
-// 32-byte records of <= 24 features with 16-byte aligned fp32 rows (F % 4 == 0, ldx == F): lane = row,
-// the row read as F / 4 float4 loads (one 64-lane instruction spans 64 consecutive rows, so the F / 4
-// loads of a wave use every byte of the lines they touch), the bins of all features searched in LDS,
-// the WHOLE record written as two 16-byte stores (bins | zero pad and (g, h): no separate memset of the
-// record array) and the feature-major bytes as one coalesced byte store per feature.
-template <int F4>
-__global__ __launch_bounds__(256) void k_bin_rec32(const float* __restrict__ X, int64_t n,
-                                                   const float* __restrict__ cuts, const int32_t* __restrict__ nbins,
-                                                   uint8_t* __restrict__ bins, uint8_t* __restrict__ binsT,
-                                                   int64_t ldt) {
-  constexpr int F = 4 * F4;
-  __shared__ float s_cuts[F * kMaxBins];
-  __shared__ int s_nb[F];
-  for (int i = threadIdx.x; i < F * kMaxBins; i += blockDim.x) s_cuts[i] = cuts[i];
-  if (threadIdx.x < F) s_nb[threadIdx.x] = nbins[threadIdx.x];
-  __syncthreads();
-  for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < n;
-       row += (int64_t)gridDim.x * blockDim.x) {
-    const float4* x4 = reinterpret_cast<const float4*>(X + row * F);
-    float v[F];
-#pragma unroll
-    for (int q = 0; q < F4; ++q) {
-      const float4 t = x4[q];
-      v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-    }
-    uint32_t w[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-      const int nb = s_nb[f];
-      uint32_t b;
-      if (v[f] != v[f]) {
-        b = kMissingBin;
-      } else {  // upper_bound over cuts[f][0..nb), clamped to nb - 1
-        const float* c = s_cuts + f * kMaxBins;
-        int lo = 0, hi = nb;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (c[mid] <= v[f]) lo = mid + 1; else hi = mid;
-        }
-        b = lo >= nb ? (uint32_t)(nb - 1) : (uint32_t)lo;
-      }
-      binsT[(int64_t)f * ldt + row] = (uint8_t)b;
-      w[f >> 2] |= b << (8 * (f & 3));
-    }
-    uint4* rec = reinterpret_cast<uint4*>(bins + row * 32);
-    rec[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    rec[1] = make_uint4(w[4], w[5], 0u, 0u);
-  }
-}
-
-COBALT_API int cobalt_bin_matrix_ld(const float* X, int64_t n, int F, int64_t ldx, const float* cuts,
-                                    const int32_t* nbins, uint8_t* bins, int stride, uint8_t* binsT, int64_t ldt,
-                                    hipStream_t stream) {
-  if (stride % 4 != 0 || stride < F || ldt < n) return -3;
-  const int grid = std::max(1, std::min(ceil_div(n, 256), 256 * 8));
-  // 32-byte records of 16-byte aligned rows: the vectorised kernel (10M x 20: 1.37 ms with k_bin)
-  if (stride == 32 && ldx == F && F % 4 == 0 && F >= 4 && F <= 24 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(bins) & 15) == 0 && knob_str(Knob::BinScalar) == nullptr) {
-    switch (F / 4) {
-#define BIN_CASE(K) \
-      case K: hipLaunchKernelGGL(k_bin_rec32<K>, dim3(grid), dim3(256), 0, stream, X, n, cuts, nbins, bins, binsT, ldt); break;
-      BIN_CASE(1) BIN_CASE(2) BIN_CASE(3) BIN_CASE(4) BIN_CASE(5) BIN_CASE(6)
-#undef BIN_CASE
-    }
-    CK_LAUNCH();
-    return 0;
-  }
-  const size_t lds = (size_t)F * kMaxBins * sizeof(float);
-  if (lds <= 64 * 1024) {
-    hipLaunchKernelGGL(k_bin<true>, dim3(grid), dim3(256), lds, stream, X, n, F, ldx, cuts, nbins, bins, stride, binsT,
-                       ldt);
-  } else {
-    hipLaunchKernelGGL(k_bin<false>, dim3(grid), dim3(256), 0, stream, X, n, F, ldx, cuts, nbins, bins, stride, binsT,
-                       ldt);
-  }
-  CK_LAUNCH();
-  return 0;
-}
-
-COBALT_API int cobalt_bin_matrix(const float* X, int64_t n, int F, int64_t ldx, const float* cuts,
-                                 const int32_t* nbins, uint8_t* bins, int stride, uint8_t* binsT,
-                                 hipStream_t stream) {
-  return cobalt_bin_matrix_ld(X, n, F, ldx, cuts, nbins, bins, stride, binsT, n, stream);
 }
 
 // Self-test of the DPP wave primitives (tests/test_gpu_gbdt.py): one wave, inclusive scans of the

@@ -149,7 +149,7 @@ def train_external(source: ChunkSource, params: GBDTParams | dict | None = None,
     dev = _resolve_device(device, None)
     if exact and dev.type == "cuda":
         # the exact pass keeps a row's node in 2^(depth + 1) - 1 <= 255 staged node slots and the feature
-        # table in LDS (csrc/gbdt.hip cobalt_gbdt_ox_init): refuse before the sketch / page passes
+        # table in LDS (csrc/gbdt_ox.h cobalt_gbdt_ox_init): refuse before the sketch / page passes
         n_feat = None
         if int(params.max_depth) <= 7:  # the feature count from the stream's first chunk (one chunk read)
             it = iter(source())

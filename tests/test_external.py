@@ -66,7 +66,7 @@ def _same_trees(a, b):
 @pytest.mark.gpu
 @pytest.mark.parametrize("colsample", [0.8, 1.0])
 def test_external_exact_streaming_gpu_equals_in_core(colsample):
-    """sample_rate=1 on the GPU: level-wise page streaming (csrc/gbdt.hip k_ox_page / k_ox_reduce + the
+    """sample_rate=1 on the GPU: level-wise page streaming (csrc/gbdt_ox.h k_ox_page / k_ox_reduce + the
     in-core k_eval), the trees of the in-core GPU fit byte for byte -- pages spilled to host DRAM, and
     partly resident in HBM. Depth 7: the deep levels' pair slots span several LDS groups (the routing
     of a row is shared by the groups' blocks), and every tree level re-streams the staging buffers."""
