@@ -14,6 +14,8 @@ Commands mirror the reference's scripts:
   bootstrap bootstrap confidence intervals of AUC, KS, ... from a CSV of labels and scores (metrics/bootstrap.py)
   calibration reliability report (ECE, Brier decomposition, Hosmer-Lemeshow) of a CSV of labels and probabilities,
             and optionally an isotonic / sigmoid calibrator fitted on it (metrics/calibration.py)
+  recourse  counterfactual recourse for a CSV of applicants: the nearest allowed change that brings each declined
+            row to the cutoff (explain/recourse.py)
 
 The artifact store is ``--store`` or ``$COBALT_ARTIFACT_URI`` (a local directory or ``s3://bucket``).
 """
@@ -259,6 +261,50 @@ def cmd_calibration(args) -> int:
     return 0
 
 
+def cmd_recourse(args) -> int:
+    """Counterfactual recourse (explain/recourse.py) for the rows of ROWS.csv: per row the nearest allowed change
+    that brings the probability of default to the cutoff, as JSON records (or CSV, by --out's suffix). The
+    policy is config.RECOURSE_POLICY with the three direction lists replaced by the flags that are given."""
+    import pandas as pd
+    import torch
+
+    from .config import ServeConfig, from_env
+    from .explain.recourse import counterfactuals, default_policy
+    from .serve.app import load_model
+
+    cfg = from_env(ServeConfig)
+    if args.model:
+        cfg.model_path, cfg.source = args.model, "local"
+    b = load_model(cfg)
+    df = pd.read_csv(args.rows)
+    names = list(b.feature_names or df.columns[: b.num_feature])
+    missing = [c for c in names if c not in df.columns]
+    if missing:
+        raise SystemExit(f"{args.rows} lacks the model's columns {missing}")
+    policy = default_policy(b)
+    for key in ("immutable", "increase_only", "decrease_only"):
+        v = getattr(args, key)
+        if v is not None:
+            policy[key] = tuple(s for s in v.split(",") if s)
+    dev = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
+    X = df[names].to_numpy(dtype="float32", na_value=float("nan"))
+    rep = counterfactuals(b, X, cutoff=args.cutoff, max_changes=args.max_changes, device=dev, **policy)
+    recs = rep.to_records()
+    if args.out and args.out.lower().endswith(".csv"):
+        flat = [{**{k: v for k, v in r.items() if k != "changes"}, "n_changes": len(r["changes"]),
+                 "changes": "; ".join(f"{c['feature']}: {c['from']:g} -> {c['to']:g}" for c in r["changes"])}
+                for r in recs]
+        pd.DataFrame(flat).to_csv(args.out, index=False)
+    elif args.out:
+        with open(args.out, "w") as fh:
+            json.dump(recs, fh)
+    else:
+        print(json.dumps(recs))
+    if args.out:
+        print(f"[INFO] wrote {args.out} ({len(recs)} rows): {json.dumps(rep.summary())}")
+    return 0
+
+
 def main(argv: list[str] | None = None) -> int:
     logging.basicConfig(level=logging.INFO, format="[%(levelname)s] %(message)s")
     p = argparse.ArgumentParser(prog="cobalt_smart_lender_ai_amd")
@@ -339,6 +385,16 @@ def main(argv: list[str] | None = None) -> int:
                    help="fit this calibrator on the column's log-odds and report the calibrated scores too")
     s.add_argument("--out", default="calibration.json", help="where --fit writes the calibrator")
     s.set_defaults(fn=cmd_calibration)
+    s = sub.add_parser("recourse", help="the nearest change that approves each declined row of ROWS.csv")
+    s.add_argument("rows", help="CSV with the model's feature columns")
+    s.add_argument("--model", default=None, help="model checkpoint (default: $COBALT_MODEL_PATH)")
+    s.add_argument("--cutoff", type=float, default=0.5, help="approve at or below this probability of default")
+    s.add_argument("--max-changes", type=int, default=1)
+    s.add_argument("--immutable", default=None, help="comma-separated features that never change")
+    s.add_argument("--increase-only", default=None, help="comma-separated features that may only grow")
+    s.add_argument("--decrease-only", default=None, help="comma-separated features that may only shrink")
+    s.add_argument("--out", default=None, help="write JSON records (or CSV, by suffix) here instead of stdout")
+    s.set_defaults(fn=cmd_recourse)
     args = p.parse_args(argv)
     return args.fn(args)
 

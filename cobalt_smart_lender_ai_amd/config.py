@@ -41,6 +41,19 @@ DEPLOYED_FEATURES = [
     "hardship_status_No Hardship",
 ]
 
+# What an applicant can change, for explain.counterfactuals on the deployed features (its keyword arguments): the
+# dummies describe the applicant's situation and stay, `term` is one of the two products, credit history can only
+# get better, the loan and the applicant's debts can only get smaller; `num_rev_accts` is free.
+RECOURSE_POLICY: dict = {
+    "immutable": ("grade_E", "home_ownership_MORTGAGE", "verification_status_Verified",
+                  "application_type_Joint App", "hardship_status_BROKEN", "hardship_status_COMPLETE",
+                  "hardship_status_COMPLETED", "hardship_status_No Hardship"),
+    "grids": {"term": (36.0, 60.0)},
+    "increase_only": ("fico_range_low", "last_fico_range_high", "emp_length_num", "earliest_cr_line_days"),
+    "decrease_only": ("loan_amnt", "installment", "open_il_12m", "open_il_24m", "max_bal_bc",
+                      "pub_rec_bankruptcies"),
+}
+
 SEARCH_SPACE: dict[str, list] = {
     "n_estimators": [100, 200, 300],
     "max_depth": [3, 5, 7, 9],

@@ -598,6 +598,23 @@ class Booster:
             out.append(res)
         return out[0] if single else out
 
+    def split_values(self, feature, n_trees: int | None = None) -> np.ndarray:
+        """The sorted distinct finite float32 split thresholds of one feature (an index or a name) in the first
+        ``n_trees`` trees (default all); empty when no tree splits on it. Along that feature, the others
+        fixed, the margin is constant between two consecutive values."""
+        f = self._feature_index(feature)
+        vals = [t.split_conditions[(~t.is_leaf) & (t.split_indices == f)]
+                for t in self.trees[: (self.num_trees if n_trees is None else n_trees)]]
+        v = np.concatenate(vals).astype(np.float32) if vals else np.zeros(0, np.float32)
+        return np.unique(v[np.isfinite(v)])
+
+    def counterfactuals(self, X, **kw):
+        """The nearest change that brings each row's probability to a cutoff:
+        :func:`~..explain.recourse.counterfactuals` with this booster as the model."""
+        from ..explain.recourse import counterfactuals
+
+        return counterfactuals(self, X, **kw)
+
     def expected_value(self) -> float:
         """TreeExplainer ``expected_value``: base margin + cover-weighted mean leaf value per tree."""
         tot = 0.0
@@ -1195,6 +1212,96 @@ def partial_dependence_host(b: Booster, X: np.ndarray, feats: Sequence[int], gri
         avg_m[k] = math.fsum(wd * m) / sw
         avg_p[k] = math.fsum(wd * p) / sw
     return ice, avg_m, avg_p
+
+
+# ------------------------------------------------------------------------ counterfactual recourse
+RECOURSE_EMPTY_BITS = 0x7FC00000  # margin bits of an empty result (idx = -1)
+
+
+def check_recourse_args(b: Booster, feats, cands, win, dirs) -> tuple[list[int], list[np.ndarray], np.ndarray,
+                                                                      np.ndarray]:
+    """The arguments of a recourse scan in canonical form, ``ValueError`` otherwise: ``feats`` A >= 1 feature
+    indices inside the model; ``cands`` one ascending NaN-free float32 vector per feature (may be empty);
+    ``win`` int32 [A, 2] inclusive candidate-index windows (default: every candidate; ``jlo > jhi`` is empty,
+    any other window must lie inside its feature's candidates); ``dirs`` int32 [A] in {-1, 0, +1} (default 0)."""
+    feats = [int(f) for f in feats]
+    A = len(feats)
+    if A < 1:
+        raise ValueError("a recourse scan needs at least one actionable feature")
+    for f in feats:
+        if not 0 <= f < b.num_feature:
+            raise ValueError(f"feature index {f} outside [0, {b.num_feature})")
+    if len(cands) != A:
+        raise ValueError(f"{A} features need {A} candidate tables, got {len(cands)}")
+    out = []
+    for cv in cands:
+        cv = np.ascontiguousarray(np.asarray(cv), dtype=np.float32)
+        if cv.ndim != 1 or np.isnan(cv).any() or (np.diff(cv) < 0).any():
+            raise ValueError("a candidate table must be an ascending vector without NaN")
+        out.append(cv)
+    if win is None:
+        win = [(0, len(cv) - 1) for cv in out]
+    win = np.ascontiguousarray(np.asarray(win), dtype=np.int32).reshape(-1, 2)
+    dirs = np.zeros(A, np.int32) if dirs is None else np.ascontiguousarray(np.asarray(dirs), dtype=np.int32).reshape(-1)
+    if win.shape[0] != A or dirs.shape[0] != A:
+        raise ValueError(f"{A} features need {A} windows and {A} directions")
+    for a in range(A):
+        jlo, jhi = int(win[a, 0]), int(win[a, 1])
+        if jlo <= jhi and (jlo < 0 or jhi >= len(out[a])):
+            raise ValueError(f"window [{jlo}, {jhi}] outside the {len(out[a])} candidates of feature {feats[a]}")
+        if int(dirs[a]) not in (-1, 0, 1):
+            raise ValueError(f"a direction is -1, 0 or +1, got {int(dirs[a])}")
+    return feats, out, win, dirs
+
+
+def recourse_scan_host(b: Booster, X: np.ndarray, feats: Sequence[int], cands: Sequence[np.ndarray], win=None,
+                       dirs=None, target: float = 0.0,
+                       n_trees: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+    """The definition of the recourse scan (CPU path and oracle of ``csrc/recourse.hip``). For row ``r`` and
+    actionable ``a`` (feature ``feats[a]``, ascending candidates ``cands[a]``, window ``[jlo, jhi] = win[a]``,
+    direction ``dirs[a]``): ``c = (number of candidates <= x) - 1`` is the row's own position and never a
+    result; ``m_j`` is :func:`predict_margin_host` of the row with that one feature replaced by candidate
+    ``j``. Returns ``(idx, margin)``, int32 and float32 ``[N, A, 3]``:
+
+    * slot 0, down: the largest ``j < c`` in the window with ``m_j <= target`` (not when ``dirs[a] == +1``);
+    * slot 1, up: the smallest ``j > c`` in the window with ``m_j <= target`` (not when ``dirs[a] == -1``);
+    * slot 2, best: the ``j != c`` in the window that the direction allows with the smallest ``m_j``; ties go
+      to the smaller ``|j - c|``, then to the smaller ``j``.
+
+    An empty result is ``idx = -1`` with the margin bits ``0x7FC00000``; a NaN ``x`` makes all three empty.
+    ``X`` is not modified."""
+    X = np.asarray(X, dtype=np.float32)
+    feats, cands, win, dirs = check_recourse_args(b, feats, cands, win, dirs)
+    N, A = X.shape[0], len(feats)
+    target = np.float32(target)
+    idx = np.full((N, A, 3), -1, dtype=np.int32)
+    margin = np.full((N, A, 3), RECOURSE_EMPTY_BITS, dtype=np.uint32).view(np.float32)
+    per_call = max(1, 65536 // max(N, 1))  # candidates scored by one predict_margin_host call
+    for a, f in enumerate(feats):
+        x = X[:, f]
+        live = ~np.isnan(x)
+        c = np.searchsorted(cands[a], x, side="right").astype(np.int64) - 1
+        best_m = np.zeros(N, np.float32)
+        jlo = int(win[a, 0])
+        for j in range(jlo, int(win[a, 1]) + 1):  # ascending: later candidates win only if strictly better
+            if (j - jlo) % per_call == 0:  # the substituted copies of X for the next candidates, one below the other
+                vals = cands[a][j:min(j + per_call, int(win[a, 1]) + 1)]
+                Xs = np.repeat(X[None, :, :], len(vals), axis=0)
+                Xs[:, :, f] = vals[:, None]
+                block = predict_margin_host(b, Xs.reshape(-1, X.shape[1]), n_trees).reshape(len(vals), N)
+            m = block[(j - jlo) % per_call]
+            below = j < c
+            ok = live & (j != c) & np.where(below, dirs[a] != 1, dirs[a] != -1)
+            hit = ok & (m <= target)
+            dn = hit & below
+            up = hit & ~below & (idx[:, a, 1] < 0)
+            bj = idx[:, a, 2].astype(np.int64)
+            be = ok & ((bj < 0) | (m < best_m) | ((m == best_m) & (np.abs(j - c) < np.abs(bj - c))))
+            for slot, sel in ((0, dn), (1, up), (2, be)):
+                idx[sel, a, slot] = j
+                margin[sel, a, slot] = m[sel]
+            best_m = np.where(be, m, best_m)
+    return idx, margin
 
 
 # ---------------------------------------------------------------------- permutation importance

@@ -1377,6 +1377,14 @@ class GBDTClassifier:
         leaf = self.get_booster().predict_leaf(self._matrix(X), device=self.device, n_trees=n)
         return leaf.cpu().numpy() if isinstance(leaf, torch.Tensor) else np.asarray(leaf)
 
+    def counterfactuals(self, X, **kw):
+        """The nearest change that brings each declined row to the cutoff
+        (:func:`~..explain.recourse.counterfactuals`), over the trees :meth:`predict_proba` scores, on this
+        estimator's device."""
+        from ..explain.recourse import counterfactuals
+
+        return counterfactuals(self, X, **kw)
+
     def refresh(self, X, y, sample_weight=None, refresh_leaf: bool = True) -> "GBDTClassifier":
         """A NEW estimator whose trees keep this model's structure and whose node statistics (and, with
         ``refresh_leaf``, leaf values) are re-estimated on ``(X, y)`` with this estimator's hyper-parameters:

@@ -3,7 +3,7 @@
 
 GPU path: gfx950 kernels in ``csrc/predict.hip`` (forest packed once per booster and device, cached),
 ``csrc/shapint.hip``, ``csrc/shapbg.hip``, ``csrc/evalcurve.hip``, ``csrc/pdp.hip``, ``csrc/permimp.hip``,
-``csrc/ale.hip`` and ``csrc/refresh.hip`` (leaf indices, leaf refresh).
+``csrc/ale.hip``, ``csrc/recourse.hip`` and ``csrc/refresh.hip`` (leaf indices, leaf refresh).
 CPU path: the NumPy reference implementations in ``models/booster.py``.
 """
 from __future__ import annotations
@@ -18,9 +18,10 @@ import torch
 from .. import _native
 from ..models.booster import (Booster, Tree, _refreshed_booster, ale_host, check_ale_edges, check_background,
                               check_eval_inputs,
-                              check_model_output, check_perm_inputs, check_refresh_inputs, eval_curve_host,
-                              partial_dependence_host, permutation_scores_host, predict_leaf_host,
-                              predict_margin_host, refresh_host, refresh_params, refresh_row_weights,
+                              check_model_output, check_perm_inputs, check_recourse_args, check_refresh_inputs,
+                              eval_curve_host, partial_dependence_host, permutation_scores_host, predict_leaf_host,
+                              predict_margin_host, recourse_scan_host, refresh_host, refresh_params,
+                              refresh_row_weights,
                               refreshed_tree, sigmoid32, staged_margins_host, treeshap_host,
                               treeshap_interactions_host, treeshap_interventional_host)
 from ..models.gbdt_host import quant_scales
@@ -111,6 +112,17 @@ _native.register("cobalt_pdp_grid_chunk", ctypes.c_int, [])
 _native.register("cobalt_pdp_chunk_rows", ctypes.c_int64, [])
 _native.register("cobalt_pdp_max_grid", ctypes.c_int, [])
 PDP_MAX_GRID = 1 << 16         # grid points per call (csrc/pdp.hip kPdpMaxGrid)
+
+# csrc/recourse.hip: (X, n, F, ldx, nodes, tree_ptr, tile_ptr, n_tiles, tile_cap, base_margin, feats_host,
+# cand_ptr_host, win_host, dir_host, feats, cand_ptr, cand_val, n_cand, win, dir, A, target, idx, margin, stream)
+_native.register("cobalt_recourse_scan", ctypes.c_int,
+                 [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p])
+_native.register("cobalt_recourse_chunk", ctypes.c_int, [])
+_native.register("cobalt_recourse_chunk_rows", ctypes.c_int64, [])
 
 # csrc/permimp.hip: (X, n, F, ldx, nodes, tree_ptr, tile_ptr, n_tiles, tile_cap, base_margin, feats, nf, cols, perm,
 # R, y, w, margins, workspace, sums, rep_chunk, stream)
@@ -617,6 +629,58 @@ def partial_dependence(b: Booster, X, feats, grids, *, n_trees: int | None = Non
         s = sums.cpu().numpy()
         am, ap = s[0:-1:2] / s[-1], s[1:-1:2] / s[-1]
     return (None if ice is None else ice.cpu().numpy()), am, ap
+
+
+# ---------------------------------------------------------------------- counterfactual recourse
+def recourse_scan_gpu(b: Booster, X: torch.Tensor, feats, cands, *, win=None, dirs=None, target_margin: float,
+                      n_trees: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Launch ``csrc/recourse.hip`` on the current stream (no host sync): for every row and every actionable
+    feature the nearest candidate below (slot 0) and above (slot 1) the row's own position whose substituted
+    margin is ``<= target_margin``, and the candidate with the lowest margin (slot 2); the definition is
+    :func:`~..models.booster.recourse_scan_host`. Returns ``(idx, margin)``, int32 and float32 ``[N, A, 3]`` on the
+    device of ``X``; margins have the bits of ``predict_margin`` on the substituted rows and ``X`` is not
+    written. ``X`` as for :func:`predict_gpu`. ``ValueError`` / ``RuntimeError`` (a model outside the kernel's LDS
+    limits) before anything is launched."""
+    _check_kernel_rows(b, X)
+    feats, cands, win, dirs = check_recourse_args(b, feats, cands, win, dirs)
+    N, F = X.shape
+    A = len(feats)
+    cand_ptr = np.zeros(A + 1, dtype=np.int64)
+    np.cumsum([len(cv) for cv in cands], out=cand_ptr[1:])
+    if cand_ptr[-1] >= 2 ** 31:
+        raise ValueError("too many candidates for one call")
+    # one int32 table on the host (checked by the entry point) and its copy on the device (read by the kernel)
+    table = np.concatenate([np.asarray(feats, np.int32), cand_ptr.astype(np.int32), win.reshape(-1), dirs])
+    table = np.ascontiguousarray(table, dtype=np.int32)
+    off = np.cumsum([0, A, A + 1, 2 * A]) * 4
+    table_d = torch.from_numpy(table).to(X.device)
+    vals = np.concatenate(cands) if cand_ptr[-1] else np.zeros(1, np.float32)
+    vals_d = torch.from_numpy(np.ascontiguousarray(vals, dtype=np.float32)).to(X.device)
+    gf = gpu_forest(b, X.device, n_trees)
+    idx = torch.empty((N, A, 3), dtype=torch.int32, device=X.device)
+    margin = torch.empty((N, A, 3), dtype=torch.float32, device=X.device)
+    hp, dp = table.ctypes.data, table_d.data_ptr()
+    rc = _native.lib().cobalt_recourse_scan(
+        X.data_ptr(), N, F, X.stride(0), gf.nodes.data_ptr(), gf.tree_ptr.data_ptr(), gf.tile_ptr.data_ptr(),
+        gf.n_tiles, gf.tile_cap, b.base_margin, *(hp + int(o) for o in off), *(dp + int(o) for o in off[:2]),
+        vals_d.data_ptr(), int(cand_ptr[-1]), dp + int(off[2]), dp + int(off[3]), A, float(np.float32(target_margin)),
+        idx.data_ptr(), margin.data_ptr(), _native.stream_handle())
+    _native.check(rc, "cobalt_recourse_scan")
+    return idx, margin
+
+
+def recourse_scan(b: Booster, X, feats, cands, *, win=None, dirs=None, target_margin: float,
+                  n_trees: int | None = None, device=None):
+    """``(idx, margin)`` of a recourse scan, [N, A, 3]: tensors on the device for a CUDA tensor ``X``, NumPy
+    otherwise. A CUDA device runs ``csrc/recourse.hip``, the CPU runs
+    :func:`~..models.booster.recourse_scan_host` (the definition)."""
+    d = _device_of(X, device)
+    if d.type != "cuda":
+        Xn = X.cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
+        return recourse_scan_host(b, Xn, feats, cands, win, dirs, target_margin, n_trees)
+    idx, margin = recourse_scan_gpu(b, _as_f32(X, d), feats, cands, win=win, dirs=dirs, target_margin=target_margin,
+                                    n_trees=n_trees)
+    return (idx, margin) if isinstance(X, torch.Tensor) else (idx.cpu().numpy(), margin.cpu().numpy())
 
 
 # ------------------------------------------------------------------------ permutation importance

@@ -9,6 +9,10 @@ Routes (identical paths, request schemas, response keys and error codes):
 * ``POST /explain_interactions``    -- additive: the ``/predict`` body -> ``{features, base_value, shap_values[20],
   interaction_values[20][20], top_pairs}``: TreeSHAP interaction values of one borrower (every row of the
   matrix sums to the feature's SHAP value); computed per request on a worker thread, not micro-batched.
+* ``POST /counterfactual``          -- additive: the ``/predict`` body, query ``cutoff`` (0.5) and ``max_changes``
+  (1) -> ``{prob_default, status, changes[{feature, from, to, cost}], total_cost, margin_before, margin_after,
+  prob_before, prob_after, ...}``: the nearest change under ``config.RECOURSE_POLICY`` that brings the borrower to
+  the cutoff (explain/recourse.py); computed per request on a worker thread, not micro-batched.
 * ``POST /predict_bulk_csv``        -- multipart field ``file`` with a CSV of the 20 columns ->
   ``{"predictions": [row + prob_default]}`` with NaN/inf rendered ``"null"``; errors -> 500
   ``"Bulk prediction failed: ..."``.
@@ -39,7 +43,7 @@ from typing import Dict, List
 
 import numpy as np
 import pandas as pd
-from fastapi import FastAPI, HTTPException, Request
+from fastapi import FastAPI, HTTPException, Query, Request
 from fastapi.responses import JSONResponse, Response
 from pydantic import BaseModel, ConfigDict, Field
 
@@ -194,6 +198,22 @@ def _interaction_values(booster: Booster, X: np.ndarray, engine=None) -> np.ndar
         return np.asarray(booster.shap_interaction_values(X, device=dev))
 
 
+def _counterfactual(booster: Booster, X: np.ndarray, cutoff: float, max_changes: int, engine=None):
+    """The recourse report of a few rows under the default policy of the deployed features: on the local
+    engine's device (serialised with the engine like :func:`_score_device`; its own buffers, no graph capture,
+    no micro-batching), else on the host."""
+    from ..explain.recourse import counterfactuals, default_policy
+
+    kw = dict(cutoff=cutoff, max_changes=max_changes, **default_policy(booster))
+    dev = getattr(engine, "device", None)
+    if dev is None or dev.type != "cuda":
+        return counterfactuals(booster, X, device="cpu", **kw)
+    import torch
+
+    with engine._lock, torch.cuda.device(dev):
+        return counterfactuals(booster, X, device=dev, **kw)
+
+
 def create_app(cfg: ServeConfig | None = None, booster: Booster | None = None) -> FastAPI:
     cfg = cfg or from_env(ServeConfig)
     state: dict = {}
@@ -279,6 +299,20 @@ def create_app(cfg: ServeConfig | None = None, booster: Booster | None = None) -
             "interaction_values": inter.tolist(),
             "top_pairs": top_interactions(inter, feats),
         })
+
+    @app.post("/counterfactual")
+    async def counterfactual(input_data: SingleInput, cutoff: float = Query(0.5, gt=0.0, lt=1.0),
+                             max_changes: int = Query(1, ge=1, le=8)):
+        row = input_data.model_dump(by_alias=True)
+        feats = state["features"]
+        X = np.array([[float(row[f]) for f in feats]], dtype=np.float32)
+        engine = None if "remote" in state else state.get("engine")  # remote scorer: this process has no device
+        loop = asyncio.get_running_loop()
+        rep = await loop.run_in_executor(None, _counterfactual, state["booster"], X, cutoff, max_changes, engine)
+        metrics.rows.labels("/counterfactual").inc()
+        rec = rep.to_records()[0]
+        return JSONResponse({"prob_default": rec["prob_before"], "cutoff": cutoff, "max_changes": max_changes,
+                             "features": feats, **rec})
 
     @app.post("/predict_bulk_csv")
     async def predict_bulk_csv(request: Request):

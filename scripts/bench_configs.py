@@ -17,6 +17,10 @@
   prep-full      the reference's full-data preprocessing (clean_data.py full + feature_engineering.py) on a
                  2.9M-row x 143-column synthetic raw export: pandas path vs the device-resident path
                  (scripts/bench_prep.py)
+  recourse-1m    counterfactual recourse (explain.counterfactuals, max_changes=1, the default policy) for 1M
+                 device-resident synthetic rows the shipped model declines: the scan kernel against the
+                 composition of per-feature ICE matrices and torch reductions (scripts/bench_recourse.py; every
+                 row is scored at ~1,150 candidate values x 300 trees)
   pipeline-100k  the reference's training job (RFE 106 -> 20 + 20 x 3-fold search + refit) end to end
                  on a 100k-row synthetic sample (scripts/bench_pipeline.py), device-resident hand-off
   pipeline-full  the same job at the reference's production scale: 2.9M raw rows -> ~2.3M training
@@ -141,6 +145,7 @@ CONFIGS = {
     "score-1b": lambda: {"config": "score-1b", "note": "one 125M-row shard of the 1B-row job (8 ranks x 125M)",
                          **_run(["-m", "cobalt_smart_lender_ai_amd.serve.batch_score", "--rows-per-gpu",
                                  "125000000"], 600)},
+    "recourse-1m": lambda: _run(["scripts/bench_recourse.py", "--rows", "1000000", "--repeats", "5"], 3400),
 }
 
 
