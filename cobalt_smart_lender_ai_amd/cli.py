@@ -16,6 +16,8 @@ Commands mirror the reference's scripts:
             and optionally an isotonic / sigmoid calibrator fitted on it (metrics/calibration.py)
   recourse  counterfactual recourse for a CSV of applicants: the nearest allowed change that brings each declined
             row to the cutoff (explain/recourse.py)
+  scorecard fit a WoE points scorecard, the transparent challenger, on a CSV and score rows with it
+            (models/scorecard.py)
 
 The artifact store is ``--store`` or ``$COBALT_ARTIFACT_URI`` (a local directory or ``s3://bucket``).
 """
@@ -305,6 +307,54 @@ def cmd_recourse(args) -> int:
     return 0
 
 
+def cmd_scorecard(args) -> int:
+    """A WoE points scorecard (models/scorecard.py) fitted on TRAIN.csv: ``scorecard.json`` and
+    ``scorecard_points.csv`` in --out; with --score, the rows of that CSV with ``score``, ``prob_default`` and
+    ``reason_1..k`` as ``scorecard_scored.csv``."""
+    import os
+
+    import pandas as pd
+    import torch
+
+    from .models.scorecard import Scorecard
+
+    df = pd.read_csv(args.train)
+    if args.label not in df.columns:
+        raise SystemExit(f"{args.train} has no column {args.label!r}")
+    cols = args.features.split(",") if args.features else [
+        c for c in df.columns if c != args.label and pd.api.types.is_numeric_dtype(df[c])]
+    missing = [c for c in cols if c not in df.columns]
+    if missing or not cols:
+        raise SystemExit(f"{args.train} lacks the columns {missing}" if missing else "no numeric feature column")
+    dev = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
+
+    def mat(frame):
+        X = frame[cols].to_numpy(dtype="float32", na_value=float("nan"))
+        return torch.as_tensor(X, device=dev) if str(dev).startswith("cuda") else X
+
+    sc = Scorecard(n_fine=args.bins, max_bins=args.max_bins, min_bin_share=args.min_bin_share, l2=args.l2,
+                   pdo=args.pdo, base_points=args.base_points, base_odds=args.base_odds)
+    sc.fit(mat(df), df[args.label].to_numpy(dtype="float32"), feature_names=cols)
+    path = sc.save(args.out)
+    sc.points_frame().to_csv(os.path.join(args.out, "scorecard_points.csv"), index=False)
+    print(f"[INFO] wrote {path} ({sc.n_kept} of {len(cols)} characteristics, {sc.fit_info['passes']} Newton passes)")
+    if args.score:
+        rows = pd.read_csv(args.score)
+        lacking = [c for c in cols if c not in rows.columns]
+        if lacking:
+            raise SystemExit(f"{args.score} lacks the columns {lacking}")
+        X = mat(rows)
+        rows["score"] = sc.score(X)
+        rows["prob_default"] = sc.predict_proba(X)[:, 1]
+        rs = sc.reasons(X, top=args.top)
+        for k in range(rs.shape[1]):
+            rows[f"reason_{k + 1}"] = [cols[f] if f >= 0 else "" for f in rs[:, k]]
+        out = os.path.join(args.out, "scorecard_scored.csv")
+        rows.to_csv(out, index=False)
+        print(f"[INFO] wrote {out} ({len(rows)} rows)")
+    return 0
+
+
 def main(argv: list[str] | None = None) -> int:
     logging.basicConfig(level=logging.INFO, format="[%(levelname)s] %(message)s")
     p = argparse.ArgumentParser(prog="cobalt_smart_lender_ai_amd")
@@ -395,6 +445,21 @@ def main(argv: list[str] | None = None) -> int:
     s.add_argument("--decrease-only", default=None, help="comma-separated features that may only shrink")
     s.add_argument("--out", default=None, help="write JSON records (or CSV, by suffix) here instead of stdout")
     s.set_defaults(fn=cmd_recourse)
+    s = sub.add_parser("scorecard", help="fit a WoE points scorecard on TRAIN.csv (and score ROWS.csv with it)")
+    s.add_argument("train", help="CSV with the label and the feature columns")
+    s.add_argument("--label", default="loan_default", help="0/1 label column (1 = bad)")
+    s.add_argument("--features", default=None, help="comma-separated feature columns (default: every numeric one)")
+    s.add_argument("--out", default="scorecard", help="directory for scorecard.json and scorecard_points.csv")
+    s.add_argument("--score", default=None, help="CSV of rows to score: adds scorecard_scored.csv")
+    s.add_argument("--top", type=int, default=4, help="reason codes per scored row (at most 8)")
+    s.add_argument("--bins", type=int, default=20, help="fine bins per feature before coarse classing")
+    s.add_argument("--max-bins", type=int, default=6)
+    s.add_argument("--min-bin-share", type=float, default=0.05)
+    s.add_argument("--l2", type=float, default=0.0)
+    s.add_argument("--pdo", type=float, default=20.0, help="points that double the odds")
+    s.add_argument("--base-points", type=float, default=600.0)
+    s.add_argument("--base-odds", type=float, default=50.0, help="odds good:bad at --base-points")
+    s.set_defaults(fn=cmd_scorecard)
     args = p.parse_args(argv)
     return args.fn(args)
 

@@ -13,6 +13,10 @@ Routes (identical paths, request schemas, response keys and error codes):
   (1) -> ``{prob_default, status, changes[{feature, from, to, cost}], total_cost, margin_before, margin_after,
   prob_before, prob_after, ...}``: the nearest change under ``config.RECOURSE_POLICY`` that brings the borrower to
   the cutoff (explain/recourse.py); computed per request on a worker thread, not micro-batched.
+* ``POST /scorecard``               -- additive: the ``/predict`` body, query ``top`` (4) -> ``{score, prob_default, margin,
+  reasons[{feature, points, max_points}], points{feature: points}, features}``: the WoE points scorecard
+  challenger (models/scorecard.py) of one borrower, read from ``scorecard.json`` beside the model; 404 when
+  there is none. One row is scored on the host.
 * ``POST /predict_bulk_csv``        -- multipart field ``file`` with a CSV of the 20 columns ->
   ``{"predictions": [row + prob_default]}`` with NaN/inf rendered ``"null"``; errors -> 500
   ``"Bulk prediction failed: ..."``.
@@ -214,7 +218,32 @@ def _counterfactual(booster: Booster, X: np.ndarray, cutoff: float, max_changes:
         return counterfactuals(booster, X, device=dev, **kw)
 
 
-def create_app(cfg: ServeConfig | None = None, booster: Booster | None = None) -> FastAPI:
+def _load_scorecard(cfg: ServeConfig):
+    """The scorecard in ``scorecard.json`` beside a local model file, or None."""
+    if cfg.source != "local":
+        return None
+    p = Path(cfg.model_path).parent / "scorecard.json"
+    if not p.exists():
+        return None
+    from ..models.scorecard import Scorecard
+
+    return Scorecard.load(p)
+
+
+def _scorecard_row(sc, X: np.ndarray, top: int) -> dict:
+    """The ``/scorecard`` response of one row (host path: a single row is not worth a launch)."""
+    m, pts, rs = sc._score_all(X, top)
+    codes = [int(c) for c in sc.encode(X)[0]]
+    names = sc.feature_names
+    row_points = {n: float(sc.points[f][codes[f]]) for f, n in enumerate(names)}
+    reasons = [{"feature": names[f], "points": row_points[names[f]], "max_points": float(sc.points[f].max())}
+               for f in (int(v) for v in rs[0]) if f >= 0]
+    score = int(pts[0]) if sc.round_points else float(sc.offset - sc.factor * m[0])
+    return {"score": score, "prob_default": float(sc.predict_proba(X)[0, 1]), "margin": float(m[0]),
+            "reasons": reasons, "points": row_points, "features": list(names)}
+
+
+def create_app(cfg: ServeConfig | None = None, booster: Booster | None = None, scorecard=None) -> FastAPI:
     cfg = cfg or from_env(ServeConfig)
     state: dict = {}
     metrics = _Metrics()
@@ -239,6 +268,7 @@ def create_app(cfg: ServeConfig | None = None, booster: Booster | None = None) -
                 batcher.on_batch = lambda n: metrics.batch_rows.observe(n)
                 state.update(engine=engine, batcher=batcher)
                 where = str(engine.device)
+            state["scorecard"] = scorecard if scorecard is not None else _load_scorecard(cfg)
             metrics.model.labels(str(bst.num_trees), str(bst.num_feature), where).set(1)
             print(f"[INFO] Model and SHAP engine ready on {where} ({bst.num_trees} trees).")
         except Exception as e:  # noqa: BLE001
@@ -313,6 +343,22 @@ def create_app(cfg: ServeConfig | None = None, booster: Booster | None = None) -
         rec = rep.to_records()[0]
         return JSONResponse({"prob_default": rec["prob_before"], "cutoff": cutoff, "max_changes": max_changes,
                              "features": feats, **rec})
+
+    @app.post("/scorecard")
+    async def scorecard_points(input_data: SingleInput, top: int = Query(4, ge=1, le=8)):
+        sc = state.get("scorecard")
+        if sc is None:
+            raise HTTPException(status_code=404, detail="No scorecard is deployed: put scorecard.json (python -m "
+                                                        "cobalt_smart_lender_ai_amd scorecard ...) beside the model.")
+        row = input_data.model_dump(by_alias=True)
+        missing = [f for f in sc.feature_names if f not in row]
+        if missing:
+            raise HTTPException(status_code=500, detail=f"The scorecard needs fields the request lacks: {missing}")
+        X = np.array([[float(row[f]) for f in sc.feature_names]], dtype=np.float32)
+        loop = asyncio.get_running_loop()
+        out = await loop.run_in_executor(None, _scorecard_row, sc, X, top)
+        metrics.rows.labels("/scorecard").inc()
+        return JSONResponse(out)
 
     @app.post("/predict_bulk_csv")
     async def predict_bulk_csv(request: Request):

@@ -122,5 +122,31 @@ def reliability_plot(report):
     return fig
 
 
+def scorecard_plot(sc, feature):
+    """One characteristic of a fitted ``models.scorecard.Scorecard`` (by name or index): bars of the WoE per bin
+    and, on a second axis, the bad rate; bins without rows are left out."""
+    f = sc.feature_names.index(feature) if isinstance(feature, str) else int(feature)
+    c = np.asarray(sc.counts[f], dtype=float)
+    tot = c.sum(0)
+    live = tot > 0
+    if not live.any():
+        raise ValueError("nothing to draw")
+    labels = [lab for lab, k in zip(sc.bin_labels(f), live) if k]
+    x = np.arange(len(labels))
+    fig, ax = plt.subplots(figsize=(7, 4))
+    ax.bar(x, np.asarray(sc.woe[f])[live], color="#377eb8", edgecolor="white")
+    ax.axhline(0.0, color="black", lw=0.8)
+    ax.set_xticks(x)
+    ax.set_xticklabels(labels, rotation=30, ha="right")
+    ax.set_ylabel("Weight of evidence")
+    ax.set_title(f"{sc.feature_names[f]}: IV {sc.iv[f]:.4f}" + (" (dropped)" if sc.dropped[f] else ""))
+    ax2 = ax.twinx()
+    ax2.plot(x, c[1][live] / tot[live], "o-", color="#e41a1c")
+    ax2.set_ylabel("Bad rate")
+    ax2.set_ylim(0.0, None)
+    fig.tight_layout()
+    return fig
+
+
 def close(fig) -> None:
     plt.close(fig)

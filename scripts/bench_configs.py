@@ -21,6 +21,9 @@
                  device-resident synthetic rows the shipped model declines: the scan kernel against the
                  composition of per-feature ICE matrices and torch reductions (scripts/bench_recourse.py; every
                  row is scored at ~1,150 candidate values x 300 trees)
+  scorecard-10m  the WoE scorecard challenger (models.Scorecard) on 10M x 20 synthetic rows: one Newton pass and the
+                 whole Newton fit through csrc/scorecard.hip against a torch composition (fp64 WoE matrix + GEMM) on
+                 the same device in the same run (scripts/bench_scorecard.py)
   pipeline-100k  the reference's training job (RFE 106 -> 20 + 20 x 3-fold search + refit) end to end
                  on a 100k-row synthetic sample (scripts/bench_pipeline.py), device-resident hand-off
   pipeline-full  the same job at the reference's production scale: 2.9M raw rows -> ~2.3M training
@@ -146,6 +149,8 @@ CONFIGS = {
                          **_run(["-m", "cobalt_smart_lender_ai_amd.serve.batch_score", "--rows-per-gpu",
                                  "125000000"], 600)},
     "recourse-1m": lambda: _run(["scripts/bench_recourse.py", "--rows", "1000000", "--repeats", "5"], 3400),
+    "scorecard-10m": lambda: {"config": "scorecard-10m",
+                              **_run(["scripts/bench_scorecard.py", "--rows", "10000000"], 1100)},
 }
 
 
