@@ -8,6 +8,20 @@
 // rows (reg&3) + 8 (reg>>2) + 4 (l>>5); each lane keeps a sorted top-K (distance, index) list in
 // registers for its half of the rows and the two halves merge at the end. Ordering is the
 // lexicographic (distance, reference index) -- deterministic, independent of the grid.
+//
+// Accuracy contract. The formula is evaluated in fp32 on the coordinates as given, so its error is
+// relative to |q|^2 + |r|^2, not to the distance: with u = 2^-24 every squared distance compared or
+// written is within (2 F + 3) u (|q|^2 + |r|^2) of the exact one (F fmas per norm, F products in the
+// dot bounded by the mean of the two norms and doubled, the two final adds). Callers therefore pass
+// coordinates centred on the column mean of R (nn/smote.py kneighbors does, in fp64, which adds the
+// rounding of each centred coordinate: (2 F + 8) u in all). Rows whose squared distances differ by
+// less than twice that bound may come out in either order; bit-identical distances (exact duplicate
+// rows) always come out by ascending index. Known limit: tight clusters far from the mean (two
+// clusters at +-1000 with spacing 0.01) are not resolved by any centring.
+//
+// k > nr is refused (-4) and inputs must be finite: an unfilled slot keeps index 0x7fffffff and
+// distance INF, a NaN distance never enters the list, and neither may leave this file --
+// k_smote_interp indexes X with what k_knn wrote.
 #include "common.h"
 
 using namespace cobalt;
@@ -135,6 +149,7 @@ COBALT_API int cobalt_knn(const float* Q, int64_t nq, const float* R, int64_t nr
   if (F < 1 || F > kMaxFk) return -1;
   if (nq <= 0) return 0;
   if (nr <= 0) return -2;
+  if (k > nr) return -4;  // the unfilled slots would be written out as index 0x7fffffff
   const dim3 grid((unsigned)ceil_div(nq, (int64_t)128));
   switch (k) {
 #define KNN_CASE(KK) \

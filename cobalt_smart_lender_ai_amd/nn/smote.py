@@ -42,24 +42,57 @@ def _device(device) -> torch.device:
 
 def kneighbors(Q: np.ndarray, R: np.ndarray, k: int, device=None) -> tuple[np.ndarray, np.ndarray]:
     """Indices [nq, k] and Euclidean distances of the k nearest rows of R for every row of Q,
-    ordered by (distance, index)."""
+    ordered by (distance, index).
+
+    Q and R are taken as float64. Raises ``ValueError`` (on every device, before any device work)
+    when ``k > len(R)`` or when Q or R holds a NaN or an infinity: scikit-learn raises for both, and
+    the kernel would hand out its "empty slot" index 2^31-1 for them.
+
+    ``device="cuda"`` (``csrc/knn.hip``) forms d^2 = |r|^2 + |q|^2 - 2 r.q in fp32, which cancels
+    badly away from the origin, so the float64 column mean mu of R is subtracted from Q and R before
+    the cast to fp32 (distances are translation-invariant). Accuracy contract of the cuda path, with
+    u = 2^-24: every squared distance it compares or returns is within
+
+        tau(q, r) = (2 F + 8) u (|q - mu|^2 + |r - mu|^2)
+
+    of the exact one, so a neighbour is certain to be found when it beats the (k+1)-th nearest by
+    more than 2 max_r tau(q, r), and rows closer together than that may come out in either order
+    (tests/knn_cases.py derives and checks this). Known limit: tau is relative to the spread of R
+    about its mean, so tight clusters far apart (two clusters at +-1000 with spacing 0.01) stay
+    unresolved -- use ``device="cpu"`` for such data. Centred coordinates too large for fp32 squared
+    distances (4 F max|x - mu|^2 >= FLT_MAX) raise ``ValueError`` too."""
     dev = _device(device)
-    Q = np.ascontiguousarray(Q, dtype=np.float32)
-    R = np.ascontiguousarray(R, dtype=np.float32)
+    Q = np.ascontiguousarray(Q, dtype=np.float64)
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    if Q.ndim != 2 or R.ndim != 2 or Q.shape[1] != R.shape[1]:
+        raise ValueError(f"Q {Q.shape} and R {R.shape} must be 2-D with the same number of columns")
+    nq, nr, F = Q.shape[0], R.shape[0], R.shape[1]
+    if k < 1 or k > nr:
+        raise ValueError(f"k={k} neighbours asked of {nr} reference rows (need 1 <= k <= rows of R)")
+    if not (np.isfinite(Q).all() and np.isfinite(R).all()):
+        raise ValueError("kneighbors: Q and R must be finite (found NaN or infinity)")
     if dev.type == "cuda":
         if k not in _KNN_K:
             raise ValueError(f"k must be one of {_KNN_K}")
-        Qd, Rd = torch.as_tensor(Q, device=dev), torch.as_tensor(R, device=dev)
-        idx = torch.empty((Q.shape[0], k), dtype=torch.int32, device=dev)
-        dist = torch.empty((Q.shape[0], k), dtype=torch.float32, device=dev)
-        rc = _native.lib().cobalt_knn(Qd.data_ptr(), Q.shape[0], Rd.data_ptr(), R.shape[0], Q.shape[1], k,
+        mu = R.mean(axis=0)
+        Qc, Rc = Q - mu, R - mu
+        big = max(float(np.abs(Qc).max(initial=0.0)), float(np.abs(Rc).max()))
+        if 4.0 * F * big * big >= float(np.finfo(np.float32).max):
+            raise ValueError(f"kneighbors: |x - mean| up to {big:.3g} overflows fp32 squared distances; use device='cpu'")
+        if nq == 0:
+            return np.empty((0, k), dtype=np.int64), np.empty((0, k), dtype=np.float32)
+        Qd = torch.as_tensor(Qc.astype(np.float32), device=dev)
+        Rd = torch.as_tensor(Rc.astype(np.float32), device=dev)
+        idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        dist = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        rc = _native.lib().cobalt_knn(Qd.data_ptr(), nq, Rd.data_ptr(), nr, F, k,
                                       idx.data_ptr(), dist.data_ptr(), _native.stream_handle())
         _native.check(rc, "cobalt_knn")
         return idx.cpu().numpy().astype(np.int64), np.sqrt(dist.cpu().numpy())
     from sklearn.neighbors import NearestNeighbors
 
-    nn = NearestNeighbors(n_neighbors=k).fit(R.astype(np.float64))
-    d, i = nn.kneighbors(Q.astype(np.float64))
+    nn = NearestNeighbors(n_neighbors=k).fit(R)
+    d, i = nn.kneighbors(Q)
     return i, d
 
 
@@ -84,6 +117,9 @@ class SMOTE:
                 continue
             Xc = Xn[yn == cls]
             k = self.k_neighbors
+            if len(Xc) <= k:
+                raise ValueError(f"SMOTE: class {cls} has {len(Xc)} rows, but k_neighbors={k} needs at least "
+                                 f"{k + 1} (every row needs k neighbours besides itself)")
             nn, _ = kneighbors(Xc, Xc, k + 1, self.device)
             nn = nn[:, 1:]
             rs = np.random.RandomState(self.random_state) if not isinstance(self.random_state, np.random.RandomState) \
