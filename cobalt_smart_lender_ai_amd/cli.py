@@ -8,6 +8,8 @@ Commands mirror the reference's scripts:
   features  stage 2 (feature_engineering.py)
   train     tree model training (model_tree_train_test.py)
   train-nn  NN challenger (notebook 04 cells 31-44)
+  explain-nn  per-row integrated-gradients attributions of the NN challenger against a background CSV
+            (explain/nn.py)
   serve     FastAPI scoring service (cobalt_fast_api.py, uvicorn)
   dictionary  descriptions of columns from the LendingClub data dictionary workbook (LCDataDictionary.xlsx)
   drift     population-stability (PSI / CSI) report of one CSV against another (monitor/drift.py)
@@ -100,8 +102,36 @@ def cmd_train_nn(args) -> int:
     from .pipeline.prep_flow import read_table
 
     m = run_nn_training(read_table(st, CLEAN_DATA_KEY_NN, args.device), cfg, store=st, local_dir=args.local_dir,
-                        device=args.device)
+                        device=args.device, explain_rows=args.explain)
     print(json.dumps({k: m[k] for k in ("auc", "auc_thresholded", "selected_features", "train_seconds")}, indent=2))
+    return 0
+
+
+def cmd_explain_nn(args) -> int:
+    """Integrated gradients (explain/nn.py) of the rows of ROWS.csv under the MLP challenger MODEL, against the
+    rows of --background: per row the base value, the model output and the contributions, as JSON records."""
+    import pandas as pd
+
+    from .explain import MLPExplainer, force_data
+    from .nn.mlp import MLPModel
+    from .nn.smote import MinMaxScaler
+
+    model = MLPModel.load(args.model)
+    rows, bg = pd.read_csv(args.rows), pd.read_csv(args.background)
+    names = list(model.feature_names or rows.columns[: model.n_features])
+    for path, df in ((args.rows, rows), (args.background, bg)):
+        missing = [c for c in names if c not in df.columns]
+        if missing:
+            raise SystemExit(f"{path} lacks the model's columns {missing}")
+    X, Z = rows[names].to_numpy(dtype="float64"), bg[names].to_numpy(dtype="float64")
+    if args.scaler:
+        with open(args.scaler) as fh:
+            scaler = MinMaxScaler.from_json(fh.read())
+        X, Z = scaler.transform(X), scaler.transform(Z)
+    ex = MLPExplainer(model, Z.astype("float32"), model_output=args.output, n_steps=args.steps, device=args.device)
+    exp = ex(X.astype("float32"))
+    exp.feature_names = names
+    print(json.dumps([force_data(exp, i) for i in range(len(X))]))
     return 0
 
 
@@ -386,7 +416,17 @@ def main(argv: list[str] | None = None) -> int:
     s.add_argument("--local-dir", default="models")
     s.add_argument("--epochs", type=int, default=50)
     s.add_argument("--use-smote", action="store_true", help="train on the SMOTE-resampled, scaled rows")
+    s.add_argument("--explain", type=int, default=0, metavar="N",
+                   help="also write shap_importance_nn.json from N validation rows (integrated gradients)")
     s.set_defaults(fn=cmd_train_nn)
+    s = sub.add_parser("explain-nn", help="integrated-gradients attributions of the NN challenger for ROWS.csv")
+    s.add_argument("model", help="nn_model.safetensors")
+    s.add_argument("rows", help="CSV with the model's feature columns")
+    s.add_argument("--background", required=True, help="CSV of background rows the attributions are taken against")
+    s.add_argument("--scaler", default=None, help="scaler_nn.json: scale both CSVs before the network sees them")
+    s.add_argument("--steps", type=int, default=32, help="midpoint steps per (row, background row) pair")
+    s.add_argument("--output", default="probability", choices=["raw", "probability"])
+    s.set_defaults(fn=cmd_explain_nn)
     s = sub.add_parser("serve")
     s.add_argument("--host", default="0.0.0.0")
     s.add_argument("--port", type=int, default=8000)

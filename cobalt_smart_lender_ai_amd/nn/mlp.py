@@ -37,6 +37,8 @@ log = logging.getLogger(__name__)
 H1, H2, H3 = 128, 32, 16
 MAX_F = 32
 MAX_F_MFMA = 31  # the MFMA trainer folds b1 into W1 through a constant-1 input column
+MAX_IG_STEPS = 4096  # integrated gradients (csrc/mlp_ig.hip): quadrature steps per (row, background row) pair
+MAX_IG_BACKGROUND = 1 << 24
 
 
 def num_params(F: int) -> int:
@@ -109,6 +111,11 @@ for _fwd in ("cobalt_mlp_forward", "cobalt_mlp_forward_mfma"):
     _native.register(_fwd, ctypes.c_int,
                      [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                       ctypes.c_void_p, ctypes.c_void_p])
+for _lim in ("cobalt_mlp_ig_max_features", "cobalt_mlp_ig_max_steps", "cobalt_mlp_ig_max_background"):
+    _native.register(_lim, ctypes.c_int, [])
+_native.register("cobalt_mlp_ig", ctypes.c_int,
+                 [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p])
 
 
 def init_params(F: int, seed: int = 0) -> np.ndarray:
@@ -224,6 +231,40 @@ def mlp_forward_gpu(X: torch.Tensor, params: torch.Tensor, out_prob: torch.Tenso
     rc = getattr(lib, name)(X.data_ptr(), X.stride(0), N, F, params.data_ptr(), out_prob.data_ptr(),
                             out_logit.data_ptr() if out_logit is not None else None, _native.stream_handle())
     _native.check(rc, name)
+
+
+def mlp_ig_gpu(X: torch.Tensor, Z: torch.Tensor, params: torch.Tensor, phi: torch.Tensor, n_steps: int,
+               probability: bool = False) -> None:
+    """Integrated gradients of fp32 rows ``X`` [N, F] against the background rows ``Z`` [B, F] (row strides
+    free, unit column stride) into the contiguous float64 ``phi`` [N, F]: the midpoint rule with ``n_steps``
+    steps per (row, background row) pair, averaged over the background, of the logit's input gradient
+    (``probability``: of its sigmoid's). ``k_mlp_ig``: forward and backward-to-the-input on fp32 MFMA, the
+    points built in registers, fp64 sums in a fixed order (the same bits for a row whatever the batch)."""
+    if X.dim() != 2 or Z.dim() != 2:
+        raise ValueError("mlp_ig_gpu needs 2-D X and Z")
+    N, F = X.shape
+    B = Z.shape[0]
+    if F < 1 or F > MAX_F:
+        raise ValueError(f"mlp_ig_gpu: 1 <= F <= {MAX_F}, got {F}")
+    if Z.shape[1] != F:
+        raise ValueError(f"mlp_ig_gpu: Z has {Z.shape[1]} columns, X has {F}")
+    if B < 1 or B > MAX_IG_BACKGROUND:
+        raise ValueError(f"mlp_ig_gpu: 1 <= background rows <= {MAX_IG_BACKGROUND}, got {B}")
+    if n_steps < 1 or n_steps > MAX_IG_STEPS:
+        raise ValueError(f"mlp_ig_gpu: 1 <= n_steps <= {MAX_IG_STEPS}, got {n_steps}")
+    for name, t in (("X", X), ("Z", Z)):
+        if t.dtype != torch.float32 or (t.shape[0] > 0 and t.stride(1) != 1):
+            raise ValueError(f"mlp_ig_gpu needs fp32 {name} with unit column stride")
+    if params.dtype != torch.float32 or not params.is_contiguous() or params.numel() != num_params(F):
+        raise ValueError("mlp_ig_gpu needs contiguous fp32 params of num_params(F) elements")
+    if phi.dtype != torch.float64 or not phi.is_contiguous() or phi.numel() < N * F:
+        raise ValueError("mlp_ig_gpu needs a contiguous float64 phi of at least N * F elements")
+    if N == 0:
+        return
+    rc = _native.lib().cobalt_mlp_ig(X.data_ptr(), X.stride(0), N, Z.data_ptr(), Z.stride(0), B, int(n_steps), F,
+                                     params.data_ptr(), int(bool(probability)), phi.data_ptr(),
+                                     _native.stream_handle())
+    _native.check(rc, "cobalt_mlp_ig")
 
 
 # ----------------------------------------------------------------------------------- training

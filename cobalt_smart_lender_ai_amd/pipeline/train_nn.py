@@ -35,6 +35,7 @@ from ..select.split import train_test_split_indices
 log = logging.getLogger(__name__)
 
 NN_OUTPUT_PATH = "models/nn/"
+EXPLAIN_BACKGROUND_ROWS = 100
 FEATURES_COMMENT = ("# Features selected using XGBoost (Some of these features are in Log scale. Refer to notebook 03 "
                     "for more details.) used for training the Neural Network model.")
 
@@ -53,7 +54,10 @@ class NNTrainConfig:
 
 
 def run_nn_training(df_nn: pd.DataFrame, cfg: NNTrainConfig | None = None, store: ArtifactStore | None = None,
-                    local_dir: str | Path = "models", device=None, gbdt_params: dict | None = None) -> dict:
+                    local_dir: str | Path = "models", device=None, gbdt_params: dict | None = None,
+                    explain_rows: int = 0) -> dict:
+    """``explain_rows > 0`` also writes ``shap_importance_nn.json``: integrated gradients (``explain.MLPExplainer``,
+    probability units) of that many validation rows against ``EXPLAIN_BACKGROUND_ROWS`` sampled training rows."""
     cfg = cfg or NNTrainConfig()
     mcfg = cfg.mlp or MLPConfig(seed=cfg.seed)
     t0 = time.perf_counter()
@@ -107,8 +111,25 @@ def run_nn_training(df_nn: pd.DataFrame, cfg: NNTrainConfig | None = None, store
                "total_seconds": time.perf_counter() - t0,
                "config": {k: v for k, v in asdict(cfg).items() if k != "mlp"} | {"mlp": asdict(mcfg)}}
     (local / "metrics_nn.json").write_text(json.dumps(metrics, indent=2, default=float))
+    names = ["nn_model.safetensors", "scaler_nn.json", "selected_features_nn.txt", "metrics_nn.json"]
+    if explain_rows > 0:
+        from ..explain.nn import MLPExplainer
+
+        pick = np.random.default_rng(cfg.seed).choice(len(fit_X), min(EXPLAIN_BACKGROUND_ROWS, len(fit_X)),
+                                                      replace=False)
+        rows = val_X[:explain_rows]
+        ex = MLPExplainer(model, fit_X[np.sort(pick)], model_output="probability", device=device)
+        phi = ex.shap_values(rows)
+        delta = ex.convergence_delta(rows)
+        imp = np.abs(phi).mean(axis=0)
+        shap_report = {"model_output": "probability", "rows": int(len(rows)), "background_rows": int(len(pick)),
+                       "n_steps": ex.n_steps, "expected_value": ex.expected_value,
+                       "max_abs_convergence_delta": float(np.abs(delta).max()) if len(rows) else 0.0,
+                       "mean_abs_shap": {f: float(v) for f, v in zip(top, imp)}}
+        (local / "shap_importance_nn.json").write_text(json.dumps(shap_report, indent=2))
+        names.append("shap_importance_nn.json")
     if store is not None:
         out = cfg.output_path
-        for name in ("nn_model.safetensors", "scaler_nn.json", "selected_features_nn.txt", "metrics_nn.json"):
+        for name in names:
             store.upload_file(local / name, out + name)
     return metrics
