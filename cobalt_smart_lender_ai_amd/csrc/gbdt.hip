@@ -25,7 +25,8 @@
 //
 // One translation unit. This file holds the in-core trainer; what is not part of its level loop is included where
 // it is needed: gbdt_bin.h (binning), gbdt_ooc.h (sampled external-memory page pass), gbdt_ox.h (exact
-// external-memory mode, after the host context).
+// external-memory mode, after the host context); of the level loop's passes the row partition (K18: k_partition,
+// k_part_pos, k_eval_part and their launches) is in gbdt_part.h.
 #include "common.h"
 #include "comm.h"
 #include "gbdt_math.h"
@@ -2382,638 +2383,7 @@ __global__ __launch_bounds__(64) void k_eval_finish_mono(GbdtDev d, int level, i
   eval_finish_node<false, kMono, kInter>(d, level, parity, ngroups, cons);
 }
 
-// ------------------------------------------------------------------------------------------
-// Partition planning + row partition (K18) + leaf margin update (K19)
-// ------------------------------------------------------------------------------------------
-// Row partition of the split nodes of a level (K18), one launch. A block takes one work item
-// (<= 8192 rows of one node); each wavefront owns a contiguous quarter and keeps its <= 32 rows per
-// lane in registers: pass 1 loads row ids + split-feature bins and counts, the block claims its
-// left range (from the node start, ascending) and right range (from the node end, descending)
-// with one atomic pair per item, pass 2 scatters with ballot ranks -- rows are read once.
-// Left rows keep their relative order inside an item; only whole items interleave, so a node's
-// row list stays sorted in 8192-row runs (the root level reads rows in identity order).
-// The per-item cursor claim is a pair of same-address device-scope atomics, whose latency /
-// serialisation across the 8 XCDs dominates a level when items are many and small (measured: removing
-// the claims took a 10M-row level from 58 to 24 us); hence 1024-thread blocks (16 waves x 8 steps per
-// 8192-row item, 4096-row items while they fit one per CU; see chunk_part).
-// kSteps: 64-row steps per wave, sized by the host to the item (chunk <= kPartWaves * kSteps * 64):
-// steps past the item would still issue their (unconditional) bin loads and ballots.
-template <int kPartWaves, int kSteps>
-__global__ __launch_bounds__(kPartWaves * 64) void k_partition(GbdtDev d, int parity, int64_t zero_next, int level,
-                                                               int chunk) {
-  constexpr int kPartSteps = kSteps;
-  BlockStamp stamp_(d);
-  __shared__ int32_t s_cnt[2][kPartWaves];
-  __shared__ int32_t s_base[2];
-  __shared__ int s_plan[5];
-  {  // zero the next level's histogram slots (hist_b of the other parity is free at this point)
-    int4* zp = reinterpret_cast<int4*>(d.zero_red ? d.zero_red : d.hist_b[parity ^ 1]);
-    const int64_t nz = zero_next / 2;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nz; e += (int64_t)gridDim.x * blockDim.x)
-      zp[e] = make_int4(0, 0, 0, 0);
-  }
-  const int item = blockIdx.x;
-  const int first = (1 << level) - 1;
-  const PlanOut pl = block_plan(1 << level, chunk, item, [&](int e) {
-    const Node& n = d.nodes[first + e];
-    const int st = n.status, cnt = n.count, start = n.start;  // loaded together (no per-load branch)
-    return (st == kSplit && cnt > 0) ? PlanEntry{first + e, 0, start, cnt} : PlanEntry{-1, 0, 0, 0};
-  }, s_plan);
-  stamp_.probe(1);
-  if (pl.node < 0) return;
-  WorkItem w;
-  w.node = pl.node;
-  w.slot = 0;
-  w.begin = pl.begin;
-  w.end = pl.end;
-  const Node nd = d.nodes[w.node];
-  const bool identity = parity == 0 && w.node == 0;
-  const int32_t* cur = d.ridx[parity];
-  int32_t* nxt = d.ridx[parity ^ 1];
-  const uint8_t* col = d.binsT + (int64_t)nd.feat * d.ldt;
-  const int j = nd.bin;
-  const bool dl = nd.default_left != 0;
-  // wave index as a uniform (SGPR) value: the per-step row counts and prefix masks stay scalar
-  const int wv = __builtin_amdgcn_readfirstlane(wave_id()), lane = lane_id();
-  const int len = w.end - w.begin;
-  const int per = ((len + kPartWaves - 1) / kPartWaves + kWave - 1) / kWave * kWave;
-  const int wb = min(w.end, w.begin + wv * per), we = min(w.end, wb + per);
-  int r[kPartSteps];
-  static_assert(kPartSteps <= 32, "step bit masks are 32-bit");
-  uint32_t lbits = 0;
-  int nl = 0, nv = 0;
-  // row ids: unconditional loads at a clamped index (w.end - 1 is a row of this item), masked after
-#pragma unroll
-  for (int k = 0; k < kPartSteps; ++k) {
-    const int i = wb + k * kWave + lane;
-    const int ic = min(i, w.end - 1);
-    const int rv = identity ? ic : cur[ic];
-    r[k] = i < we ? rv : -1;
-  }
-  // the split feature's bins: unconditional loads (padding rows read row 0), so all kPartSteps are in
-  // flight at once -- a load guarded per step made hipcc wait for each in turn (32 round trips)
-  uint8_t bv[kPartSteps];
-#pragma unroll
-  for (int k = 0; k < kPartSteps; ++k) bv[k] = col[max(r[k], 0)];
-  // Pass 1 in integer arithmetic (boolean forms compiled to per-step branches and spilled masks): the
-  // direction bit of each row (bin <= j, or the default direction for the missing code) goes to bit k of
-  // lbits (0 for the padding lanes, r = -1). The valid rows of step k are a prefix of the lanes (rows
-  // wb + 64 k + lane < we), so the wave's valid count is we - wb.
-  const int jm1 = j + 1;  // left <=> bin - (j + 1) < 0
-  const uint32_t dlv = dl ? 1u : 0u;
-  nv = max(0, we - wb);
-#pragma unroll
-  for (int k = 0; k < kPartSteps; ++k) {
-    const uint32_t b = bv[k];
-    const uint32_t lt = (uint32_t)((int)b - jm1) >> 31;  // bin <= j
-    const uint32_t ms = (b + 1u) >> 8;                    // bin == 255 (missing)
-    const uint32_t ok = ~(uint32_t)r[k] >> 31;            // a row, not padding
-    const uint32_t left = (lt | (ms & dlv)) & ok;
-    lbits |= left << k;
-    nl += __popcll(__ballot(left != 0u));
-  }
-  asm volatile("" : "+v"(lbits));  // pass 2 reads the packed bits (not 32 live per-step values)
-  if (lane == 0) { s_cnt[0][wv] = nl; s_cnt[1][wv] = nv - nl; }
-  __syncthreads();
-  stamp_.probe(2);
-  if (threadIdx.x == 0) {
-    int tl = 0, tr = 0;
-    for (int k = 0; k < kPartWaves; ++k) { tl += s_cnt[0][k]; tr += s_cnt[1][k]; }
-    if (d.ablate == 12) {  // timing-only: no cursor atomics
-      s_base[0] = 0; s_base[1] = 0;
-    } else {  // both cursors in one 64-bit claim (left = low word, right = high word)
-      const unsigned long long c = atomicAdd(reinterpret_cast<unsigned long long*>(d.cursors + 2 * w.node),
-                                             ((unsigned long long)(uint32_t)tr << 32) | (uint32_t)tl);
-      s_base[0] = (int32_t)(uint32_t)c;
-      s_base[1] = (int32_t)(c >> 32);
-    }
-  }
-  __syncthreads();
-  stamp_.probe(3);
-  int bl = s_base[0], br = s_base[1];
-  for (int k = 0; k < wv; ++k) { bl += s_cnt[0][k]; br += s_cnt[1][k]; }
-  // Pass 2: one destination per lane (left rows ascending from the node start, right rows descending
-  // from its end), one store per step under the valid-lane mask.
-  uint32_t pl_ = (uint32_t)(nd.start + bl);                 // next left slot
-  uint32_t pr_ = (uint32_t)(nd.start + nd.count - 1 - br);  // next right slot (descending)
-#pragma unroll
-  for (int k = 0; k < kPartSteps; ++k) {
-    const bool valid = r[k] >= 0;
-    const uint32_t left = (lbits >> k) & 1u;
-    const uint64_t lm = __ballot(left != 0u), vm = __ballot(valid);
-    const uint32_t rk_l = mask_rank(lm);
-    // valid lanes are a prefix: a right row's rank among the right rows is lane - rk_l
-    const uint32_t dst = rk_l + (left ? pl_ : pr_ - (uint32_t)lane);
-    if (valid) store_wt(nxt + dst, r[k], (d.wt & 2) != 0);
-    const uint32_t cl = (uint32_t)__popcll(lm);
-    pl_ += cl;
-    pr_ -= (uint32_t)__popcll(vm) - cl;
-  }
-}
-
-// Row partition by POSITION (levels with <= 64 nodes): block b takes the row-id positions [b C, (b + 1) C)
-// of the level's ridx buffer (C = 16 waves x kSteps x 64), whatever nodes they belong to. A level's nodes
-// own disjoint, position-ordered ranges of that buffer (every child range lies inside its parent's), so the
-// block's row-id loads depend on nothing but the block index: they are issued at kernel entry, in the same
-// round trip as the level's node records -- where the node-ordered k_partition first plans its item from
-// the node table and only then loads its row ids (~1.1-1.4 us per block at 10M rows, one of ~4 dependent
-// round trips). A wave's 512 positions cover a few ranges: a uniform walk over the split ranges that start
-// before each 64-row step gives every lane its node; positions of leaves (and gaps) route nowhere. Counts
-// are kept per (wave, range) in LDS, one cursor claim per range per block (all in one round trip), and the
-// scatter advances per-(wave, range) pointers as k_partition's per-wave ones (left rows ascending from the
-// node start, right rows descending from its end).
-constexpr int kPartPosNodes = 64;
-
-template <int kSteps>
-__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void k_part_pos(GbdtDev d, int parity, int64_t zero_next, int level) {
-  constexpr int kPW = 16;
-  constexpr int kN = kPartPosNodes;
-  BlockStamp stamp_(d);
-  __shared__ int s_rs[kN], s_re[kN];  // split ranges (position order): start, end
-  __shared__ uint32_t s_rm[kN];        // feature | (j + 1) << 16 | dl << 25
-  __shared__ int s_rn[kN];             // node index
-  __shared__ int s_nr;
-  __shared__ int32_t s_cnt[kPW][kN][2];  // per (wave, range): left / right rows, then the wave's scatter bases
-  __shared__ int s_one, s_one_node, s_one_start, s_one_end;  // the block's one range (s_one < 0: several)
-  __shared__ uint32_t s_one_meta;
-  __shared__ int32_t s_wc[2][kPW];
-  __shared__ int32_t s_wbase[2];
-  {  // zero the next level's histogram slots (hist_b of the other parity is free at this point)
-    int4* zp = reinterpret_cast<int4*>(d.zero_red ? d.zero_red : d.hist_b[parity ^ 1]);
-    const int64_t nz = zero_next / 2;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nz; e += (int64_t)gridDim.x * blockDim.x)
-      zp[e] = make_int4(0, 0, 0, 0);
-  }
-  const int n = (int)d.n;
-  const int wv = __builtin_amdgcn_readfirstlane(wave_id()), lane = lane_id();
-  const int wb = blockIdx.x * (kPW * kSteps * kWave) + wv * (kSteps * kWave);
-  const bool identity = parity == 0 && level == 0;  // the root's rows in identity order (never written)
-  const int32_t* cur = d.ridx[parity];
-  int32_t* nxt = d.ridx[parity ^ 1];
-  // row ids first: unconditional loads at clamped positions (no dependence on the node table)
-  int r[kSteps];
-#pragma unroll
-  for (int k = 0; k < kSteps; ++k) {
-    const int p = min(wb + k * kWave + lane, n - 1);
-    r[k] = identity ? p : cur[p];
-  }
-  // the level's split nodes with rows -> LDS, in position order (wave 0, one lane per node)
-  const int first = (1 << level) - 1, nlev = 1 << level;
-  if (wv == 0) {
-    const int e = lane;
-    const Node& nd = d.nodes[first + min(e, nlev - 1)];
-    const int st = nd.status, start = nd.start, cnt = nd.count, f = nd.feat, j = nd.bin, dl = nd.default_left;
-    const bool on = e < nlev && st == kSplit && cnt > 0;
-    const uint64_t m = __ballot(on);
-    if (on) {
-      const int k = mask_rank(m);
-      s_rs[k] = start;
-      s_re[k] = start + cnt;
-      s_rm[k] = (uint32_t)f | ((uint32_t)(j + 1) & 0x1FFu) << 16 | (uint32_t)(dl & 1) << 25;
-      s_rn[k] = first + e;
-    }
-    if (e == 0) s_nr = __popcll(m);
-    // the block's positions inside ONE split range (nearly every block: a node's range spans ~10^5 rows)?
-    const int b0 = blockIdx.x * (kPW * kSteps * kWave), b1 = min(n, b0 + kPW * kSteps * kWave);
-    const uint64_t hit = __ballot(on && start <= b0 && start + cnt >= b1);
-    if (e == 0) s_one = hit ? __ffsll((unsigned long long)hit) - 1 : -1;
-    if (hit && e == __ffsll((unsigned long long)hit) - 1) {
-      s_one_node = first + e;
-      s_one_start = start;
-      s_one_end = start + cnt;
-      s_one_meta = (uint32_t)f | ((uint32_t)(j + 1) & 0x1FFu) << 16 | (uint32_t)(dl & 1) << 25;
-    }
-  }
-  for (int i = threadIdx.x; i < kPW * kN * 2; i += blockDim.x) (&s_cnt[0][0][0])[i] = 0;
-  __syncthreads();
-  stamp_.probe(1);
-  const int nr = s_nr;
-  if (nr == 0) return;
-  if (s_one >= 0) {
-    // One range: k_partition's per-wave passes (counts by ballot, one claim, running per-wave pointers)
-    const int node = s_one_node, nstart = s_one_start, nend = s_one_end;
-    const uint32_t m = s_one_meta;
-    const uint8_t* col = d.binsT + (int64_t)(m & 0xFFFFu) * d.ldt;
-    uint8_t bv1[kSteps];
-#pragma unroll
-    for (int k = 0; k < kSteps; ++k) bv1[k] = col[r[k]];
-    const int jm1 = (int)((m >> 16) & 0x1FFu);
-    const uint32_t dlv = (m >> 25) & 1u;
-    const int nv = max(0, min(n, wb + kSteps * kWave) - wb);  // valid positions of this wave (a prefix)
-    uint32_t lb = 0;
-    int nl = 0;
-#pragma unroll
-    for (int k = 0; k < kSteps; ++k) {
-      const uint32_t b = bv1[k];
-      const uint32_t lt = (uint32_t)((int)b - jm1) >> 31;
-      const uint32_t ms = (b + 1u) >> 8;
-      const uint32_t ok = (uint32_t)(k * kWave + lane < nv);
-      const uint32_t left = (lt | (ms & dlv)) & ok;
-      lb |= left << k;
-      nl += __popcll(__ballot(left != 0u));
-    }
-    asm volatile("" : "+v"(lb));
-    if (lane == 0) { s_wc[0][wv] = nl; s_wc[1][wv] = nv - nl; }
-    __syncthreads();
-    stamp_.probe(2);
-    if (threadIdx.x == 0) {
-      int tl = 0, tr = 0;
-      for (int k = 0; k < kPW; ++k) { tl += s_wc[0][k]; tr += s_wc[1][k]; }
-      const unsigned long long c =
-          d.ablate == 12 ? 0ull
-                         : atomicAdd(reinterpret_cast<unsigned long long*>(d.cursors + 2 * node),
-                                     ((unsigned long long)(uint32_t)tr << 32) | (uint32_t)tl);
-      s_wbase[0] = (int32_t)(uint32_t)c;
-      s_wbase[1] = (int32_t)(c >> 32);
-    }
-    __syncthreads();
-    stamp_.probe(3);
-    int bl = s_wbase[0], br = s_wbase[1];
-    for (int k = 0; k < wv; ++k) { bl += s_wc[0][k]; br += s_wc[1][k]; }
-    uint32_t pl_ = (uint32_t)(nstart + bl);
-    uint32_t pr_ = (uint32_t)(nend - 1 - br);
-#pragma unroll
-    for (int k = 0; k < kSteps; ++k) {
-      const bool valid = k * kWave + lane < nv;
-      const uint32_t left = (lb >> k) & 1u;
-      const uint64_t lm = __ballot(left != 0u), vm = __ballot(valid);
-      const uint32_t rk_l = mask_rank(lm);
-      const uint32_t dst = rk_l + (left ? pl_ : pr_ - (uint32_t)lane);
-      if (valid) store_wt(nxt + dst, r[k], (d.wt & 2) != 0);
-      const uint32_t cl = (uint32_t)__popcll(lm);
-      pl_ += cl;
-      pr_ -= (uint32_t)__popcll(vm) - cl;
-    }
-    return;
-  }
-  // first range that ends past the wave's first position (uniform binary search over the LDS ends)
-  int k0 = 0;
-  {
-    int lo = 0, hi = nr;  // first k with re[k] > wb
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (__builtin_amdgcn_readfirstlane(s_re[mid]) > wb) hi = mid; else lo = mid + 1;
-    }
-    k0 = lo;
-  }
-  // pass 1: each lane's range (uniform walk over the ranges that start inside or before the step), the
-  // split feature's bin, the direction; per (wave, range) counts
-  // each row's range, packed 8 bits per step (0xFF: routes nowhere) -- 2 VGPRs instead of kSteps (the kernel
-  // must stay within 64 VGPRs for two 1024-thread blocks per CU)
-  uint32_t klp[(kSteps + 3) / 4];
-#pragma unroll
-  for (int i = 0; i < (kSteps + 3) / 4; ++i) klp[i] = 0xFFFFFFFFu;
-  auto kl_of = [&](int k) -> int {
-    const uint32_t v = (klp[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-    return v == 0xFFu ? -1 : (int)v;
-  };
-  uint32_t lbits = 0, inbits = 0;
-  uint8_t bv[kSteps];
-  // Fast path (nearly every wave: a node's range spans ~10^5 positions): the wave's positions lie inside one
-  // range -- every lane's node is k0, no per-lane search. Otherwise each lane binary-searches the ranges
-  // from k0 on (the last one starting at or before its position) and checks the range's end.
-  const bool one = k0 < nr && __builtin_amdgcn_readfirstlane(s_rs[k0]) <= wb &&
-                   __builtin_amdgcn_readfirstlane(s_re[k0]) >= wb + kSteps * kWave;
-  if (one) {
-    const uint32_t m = __builtin_amdgcn_readfirstlane(s_rm[k0]);
-    const uint8_t* col = d.binsT + (int64_t)(m & 0xFFFFu) * d.ldt;
-#pragma unroll
-    for (int k = 0; k < kSteps; ++k) {
-      klp[k >> 2] &= ~((uint32_t)(0xFFu ^ (uint32_t)k0) << (8 * (k & 3)));
-      bv[k] = col[max(r[k], 0)];
-    }
-    inbits = (1u << kSteps) - 1u;
-  } else {
-#pragma unroll
-    for (int k = 0; k < kSteps; ++k) {
-      const int p = wb + k * kWave + lane;
-      int lo = k0, hi = nr - 1, kk = -1;  // last t in [k0, nr) with rs[t] <= p
-      while (lo <= hi) {
-        const int mid = (lo + hi) >> 1;
-        if (s_rs[mid] <= p) { kk = mid; lo = mid + 1; } else hi = mid - 1;
-      }
-      const bool in = kk >= 0 && p < n && p < s_re[max(kk, 0)];
-      if (in) klp[k >> 2] &= ~((uint32_t)(0xFFu ^ (uint32_t)kk) << (8 * (k & 3)));
-      inbits |= (in ? 1u : 0u) << k;
-      // the split feature's bin: an unconditional load (lanes outside a range read their nearest one's column)
-      const uint32_t m = s_rm[max(kk, 0)];
-      bv[k] = d.binsT[(int64_t)(m & 0xFFFFu) * d.ldt + max(r[k], 0)];
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < kSteps; ++k) {
-    const int klk = kl_of(k);
-    const uint32_t m = s_rm[max(klk, 0)];
-    const uint32_t b = bv[k];
-    const int jm1 = (int)((m >> 16) & 0x1FFu);  // j + 1
-    const uint32_t lt = (uint32_t)((int)b - jm1) >> 31;
-    const uint32_t ms = (b + 1u) >> 8;
-    const uint32_t left = (lt | (ms & ((m >> 25) & 1u))) & ((inbits >> k) & 1u);
-    lbits |= left << k;
-    // per-range counts of this step (uniform loop over the ranges present in it; usually one)
-    uint64_t rem = __ballot((inbits >> k) & 1u);
-    const uint64_t lm = __ballot(left != 0u);
-    while (rem) {
-      const int src = __ffsll((unsigned long long)rem) - 1;
-      const int kk = __builtin_amdgcn_readlane(klk, src);
-      const uint64_t mk = __ballot(klk == kk) & rem;
-      if (lane == 0) {
-        s_cnt[wv][kk][0] += __popcll(mk & lm);
-        s_cnt[wv][kk][1] += __popcll(mk & ~lm);
-      }
-      rem &= ~mk;
-    }
-  }
-  __syncthreads();
-  stamp_.probe(2);
-  // one claim per range for the whole block (thread t: range t), then each wave's bases
-  if ((int)threadIdx.x < nr) {
-    const int t = threadIdx.x;
-    int tl = 0, tr = 0;
-    for (int w = 0; w < kPW; ++w) { tl += s_cnt[w][t][0]; tr += s_cnt[w][t][1]; }
-    if (tl + tr > 0) {
-      const unsigned long long c =
-          d.ablate == 12 ? 0ull
-                         : atomicAdd(reinterpret_cast<unsigned long long*>(d.cursors + 2 * s_rn[t]),
-                                     ((unsigned long long)(uint32_t)tr << 32) | (uint32_t)tl);
-      int bl = s_rs[t] + (int)(uint32_t)c;                // next left slot
-      int br = s_re[t] - 1 - (int)(uint32_t)(c >> 32);    // next right slot (descending)
-      for (int w = 0; w < kPW; ++w) {
-        const int cl = s_cnt[w][t][0], cr = s_cnt[w][t][1];
-        s_cnt[w][t][0] = bl;
-        s_cnt[w][t][1] = br;
-        bl += cl;
-        br -= cr;
-      }
-    }
-  }
-  __syncthreads();
-  stamp_.probe(3);
-  // pass 2: scatter with ballot ranks inside each (step, range)
-#pragma unroll
-  for (int k = 0; k < kSteps; ++k) {
-    const bool in = (inbits >> k) & 1u;
-    const uint32_t left = (lbits >> k) & 1u;
-    const int klk = kl_of(k);
-    uint64_t rem = __ballot(in);
-    const uint64_t lm = __ballot(left != 0u);
-    while (rem) {
-      const int src = __ffsll((unsigned long long)rem) - 1;
-      const int kk = __builtin_amdgcn_readlane(klk, src);
-      const uint64_t mk = __ballot(klk == kk) & rem;
-      const int pl = __builtin_amdgcn_readfirstlane(s_cnt[wv][kk][0]);
-      const int pr = __builtin_amdgcn_readfirstlane(s_cnt[wv][kk][1]);
-      const uint64_t ml = mk & lm, mr = mk & ~lm;
-      if (klk == kk) {
-        const int dst = left ? pl + mask_rank(ml) : pr - mask_rank(mr);
-        store_wt(nxt + dst, r[k], (d.wt & 2) != 0);
-      }
-      if (lane == 0) {
-        s_cnt[wv][kk][0] = pl + __popcll(ml);
-        s_cnt[wv][kk][1] = pr - __popcll(mr);
-      }
-      rem &= ~mk;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// Split evaluation fused with the row partition (one GPU, a level's items <= CUs, levels 0 .. max_depth - 2).
-// At small row counts a level is a chain of short launches whose fixed costs dominate (1M rows:
-// k_eval ~6.6 us + a ~1.5 us boundary per level), so every block of the partition pass evaluates its
-// OWN node (the same eval_core, redundantly: ~2 us of fp64 work per block on its own CU, with the
-// node's ~42 KB of histograms hot in L2) and partitions its rows by the result -- one launch per level
-// fewer. The item's row ids are loaded before the evaluation (they do not depend on the split), so
-// their latency hides behind it. The block holding the node's first item finalises the node record
-// and stores its histogram for the children (eval_finalize / eval_core's store, as k_eval does).
-// The plan covers every node of the level with rows (a block that finalised its node changes the
-// status from active to split / leaf; the other blocks accept any status but kNone). A leaf's blocks
-// stop after the evaluation.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool split_decision(const GbdtDev& d, const Cand& best, int nb, int& f, int& j, bool& dl) {
-  const float loss = (float)best.gain;
-  const bool ok = best.key != 0x7fffffff && loss > 1e-6f && loss >= (float)d.gamma;
-  f = best.key >> 10;
-  const int r = best.key & 1023;
-  if (r < 512) { j = r; dl = false; } else { j = (nb - 1 - (r - 512)) - 1; dl = true; }
-  return ok;
-}
-
-// A node's split decision as ONE 8-byte granule {tag, decision} (evaluator-block modes): written by the
-// node's evaluator block with a write-through store, polled by the node's partition blocks.
-__device__ __forceinline__ uint64_t decision_word(uint32_t tag, bool ok, bool fail, int f, int j, bool dl) {
-  const uint32_t v = (ok ? 1u : 0u) | (fail ? 2u : 0u) | (dl ? 4u : 0u) | ((uint32_t)(j + 1) & 0x3FFu) << 3 |
-                     (uint32_t)f << 13;
-  return ((uint64_t)tag << 32) | v;
-}
-
-// Every block evaluates its node (the items fit one block per CU):
-//   kMode 0: one GPU. 1: data parallel with the level's global histograms already in hist_b (RCCL / the
-//   separate IPC exchange kernel); every active node gets an item (possibly empty), so each rank
-//   finalises every node of the level, also those it holds no rows of.
-// kMode 2, EVALUATOR blocks (data parallel over the fused IPC exchange): blocks 0 .. 2^level - 1
-// evaluate one node position each, exactly as k_eval<false, true, true> does (block 0 publishes the
-// epoch, every evaluator sums its node's cells over the ranks; node ownership on the deep levels; the
-// replica digest), publish its decision granule and finalise it; the blocks after them are the
-// partition items, which plan and load their row ids while the evaluation runs and then poll their
-// node's granule (one lane, bounded by the group's deadline). One evaluation per node -- no xGMI
-// traffic multiplied by the items -- and no k_eval -> k_partition boundary, at any item count: blocks
-// are dispatched in index order on every XCD, so the evaluators hold CUs before any item does, and no
-// evaluator waits on an item. (The same form for one GPU beyond one block per CU measured slower than
-// k_eval + k_partition -- 10M rows 238.6 vs 231.9 ms: the fused kernel's 110 VGPRs hold the partition
-// to one block per CU; profiles/round5/eval_blocks_10M.txt.)
-template <int kSteps, int kMode>
-__global__ __launch_bounds__(1024) void k_eval_part(GbdtDev d, int parity, int64_t zero_next, int level, int chunk,
-                                                    int tree, EvalSlots es, uint32_t tag) {
-  constexpr bool kDP = kMode != 0;
-  constexpr bool kEvalBlocks = kMode == 2;
-  constexpr bool kIpc = kMode == 2;
-  constexpr int kPW = 16;  // waves
-  BlockStamp stamp_(d);
-  __shared__ int32_t s_cnt[2][kPW];
-  __shared__ int32_t s_base[2];
-  __shared__ EvalOut s_out;
-  // zero the next level's reduce destination (hist_b of the other parity, or the next IPC send slot;
-  // kMode 2: the evaluators do, see below)
-  int4* zp = reinterpret_cast<int4*>(d.zero_red ? d.zero_red : d.hist_b[parity ^ 1]);
-  const int64_t nz = zero_next / 2;
-  if (!kIpc)
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nz; e += (int64_t)gridDim.x * blockDim.x)
-      zp[e] = make_int4(0, 0, 0, 0);
-  const int nlev = 1 << level;
-  const int first = nlev - 1;
-  if (kIpc && (int)blockIdx.x < nlev) {  // the evaluator of node first + blockIdx.x
-    const int pos = blockIdx.x, n = first + pos;
-    const IpcFusedView* iv = d.ipcv + (d.ipc_epoch & 1u);
-    const bool owned = d.own_level >= 0 && level >= d.own_level;
-    const bool mine = !owned || node_owner(d, level, n, iv->n) == iv->me;
-    const bool good = eval_core<false, true, true>(d, level, parity, tree, d.F, es, pos, stamp_, &s_out);
-    if (threadIdx.x == 0) {
-      if (good) {  // the decision first (the items wait on it; they need nothing else of the finalisation)
-        int f = 0, j = -1;
-        bool dl = false;
-        const bool ok = split_decision(d, s_out.best, s_out.nb, f, j, dl);
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(d.dec) + n,
-                           (unsigned long long)decision_word(tag, ok, false, f, j, dl), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        eval_finalize<true>(d, level, n, s_out.G, s_out.H, s_out.best, s_out.cut, s_out.nb);
-        if (owned) own_publish(d, iv, n);
-      } else {
-        const Node nd = d.nodes[n];  // a non-owner's copy of the owner's record (own_copy), or inactive
-        if (owned && mine && nd.status != kActive) own_publish(d, iv, n);  // (as k_eval: a diverged peer learns)
-        const bool failed =
-            __hip_atomic_load(iv->myflag + kIpcStickyWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-        // Always published: a node that is inactive here has no items, but one this rank planned items
-        // for can come back inactive from its owner's record (a diverged replica) -- its items then
-        // route no rows (and the replica digest reports the divergence at the next tree) instead of
-        // waiting for a decision that never comes.
-        const uint64_t w = decision_word(tag, nd.status == kSplit, failed || nd.status == kActive, nd.feat, nd.bin,
-                                         nd.default_left != 0);
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(d.dec) + n, (unsigned long long)w, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    // The next send slot (this epoch - 1's) is zeroed once every peer has published this epoch: a peer
-    // then has finished reading its previous contents. The evaluators that exchanged waited for that in
-    // eval_core; a non-owner (it waited only for its node's owner) polls the flags once more, after its
-    // decision is out. A failed exchange zeroes nothing (the fit is aborted).
-    const bool synced =
-        mine ? __hip_atomic_load(iv->myflag + kIpcStickyWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u
-             : ipc_wait<false>(iv->ftab, iv->n, iv->me, iv->myflag, d.ipc_epoch, iv->err_host, iv->timeout);
-    if (!synced) return;
-    for (int64_t e = (int64_t)pos * blockDim.x + threadIdx.x; e < nz; e += (int64_t)nlev * blockDim.x)
-      zp[e] = make_int4(0, 0, 0, 0);
-    return;
-  }
-  const int item = kEvalBlocks ? (int)blockIdx.x - nlev : (int)blockIdx.x;
-  // this block's item: the root's rows are fixed slices; deeper levels' items are planned by every
-  // block (block_plan over the level's node table)
-  PlanOut pl;
-  __shared__ int s_plan[5];
-  if (level == 0) {
-    const int n = (int)d.n, b = item * chunk;
-    const int items = max((n + chunk - 1) / chunk, kDP ? 1 : 0);
-    pl = PlanOut{item < items ? 0 : -1, 0, min(b, n), min(n, b + chunk), items};
-  } else {
-    pl = block_plan<kDP>(1 << level, chunk, item, [&](int e) {
-      const Node& n = d.nodes[first + e];
-      const int st = n.status, cnt = n.count, start = n.start;  // loaded together (no per-load branch)
-      return (st != kNone && (kDP || cnt > 0)) ? PlanEntry{first + e, 0, start, cnt} : PlanEntry{-1, 0, 0, 0};
-    }, s_plan);
-  }
-  if (pl.node < 0) return;
-  const int node = pl.node;
-  // the item's row ids and the node's range: independent of the split, in flight during the evaluation
-  const bool identity = parity == 0 && node == 0;
-  const int32_t* cur = d.ridx[parity];
-  int32_t* nxt = d.ridx[parity ^ 1];
-  const int wv = __builtin_amdgcn_readfirstlane(wave_id()), lane = lane_id();
-  const int len = pl.end - pl.begin;
-  const int per = ((len + kPW - 1) / kPW + kWave - 1) / kWave * kWave;
-  const int wb = min(pl.end, pl.begin + wv * per), we = min(pl.end, wb + per);
-  int r[kSteps];
-  auto load_rows = [&]() {
-#pragma unroll
-    for (int k = 0; k < kSteps; ++k) {
-      const int i = wb + k * kWave + lane;
-      const int ic = max(min(i, pl.end - 1), 0);
-      const int rv = identity ? ic : cur[ic];
-      r[k] = i < we ? rv : -1;
-    }
-  };
-  const int nstart = d.nodes[node].start, ncount = d.nodes[node].count;
-  const bool lead = pl.begin == nstart;  // the node's first item
-  int f, j;
-  bool dlb, ok;
-  load_rows();
-  if constexpr (kEvalBlocks) {  // the node's evaluator decides; the row ids are in flight meanwhile
-    if (len == 0) return;
-    __shared__ uint32_t s_dec;
-    if (threadIdx.x == 0) {
-      // (bounded: the exchange's deadline; without an exchange 20 s, which no evaluator approaches)
-      const IpcFusedView* iv = kIpc ? d.ipcv + (d.ipc_epoch & 1u) : nullptr;
-      const uint64_t limit = kIpc ? iv->timeout : 2000000000ull;
-      const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-      uint32_t v = 2u;  // failed unless the evaluator's granule arrives
-      for (;;) {
-        const uint64_t w = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(d.dec) + node,
-                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((uint32_t)(w >> 32) == tag) { v = (uint32_t)w; break; }
-        if (__builtin_amdgcn_s_memrealtime() - t0 > limit) {
-          if (kIpc) ipc_fail(iv->myflag, iv->err_host);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-      s_dec = v;
-    }
-    __syncthreads();
-    const uint32_t v = s_dec;
-    if (v & 2u) return;  // the exchange failed (the host watchdog reports it)
-    ok = (v & 1u) != 0;
-    dlb = (v & 4u) != 0;
-    j = (int)((v >> 3) & 0x3FFu) - 1;
-    f = (int)(v >> 13);
-  } else {
-    // every block evaluates its node itself (the histograms are L2-hot; the row ids are in flight)
-    eval_core<false, false, kDP, true>(d, level, parity, tree, d.F, es, node - first, stamp_, &s_out, lead);
-    __syncthreads();
-    const Cand best = s_out.best;
-    ok = split_decision(d, best, s_out.nb, f, j, dlb);
-    if (lead && threadIdx.x == 0) eval_finalize<kDP>(d, level, node, s_out.G, s_out.H, best, s_out.cut, s_out.nb);
-  }
-  stamp_.probe(4);
-  if (!ok || len == 0) return;  // a leaf (its rows are not routed) or an empty item (block-uniform)
-  const uint8_t* col = d.binsT + (int64_t)f * d.ldt;
-  uint8_t bv[kSteps];
-#pragma unroll
-  for (int k = 0; k < kSteps; ++k) bv[k] = col[max(r[k], 0)];
-  // pass 1 / claim / pass 2: k_partition's integer-arithmetic form
-  const int jm1 = j + 1;
-  const uint32_t dlv = dlb ? 1u : 0u;
-  const int nv = max(0, we - wb);
-  uint32_t lbits = 0;
-  int nl = 0;
-#pragma unroll
-  for (int k = 0; k < kSteps; ++k) {
-    const uint32_t b = bv[k];
-    const uint32_t lt = (uint32_t)((int)b - jm1) >> 31;
-    const uint32_t ms = (b + 1u) >> 8;
-    const uint32_t okr = ~(uint32_t)r[k] >> 31;
-    const uint32_t left = (lt | (ms & dlv)) & okr;
-    lbits |= left << k;
-    nl += __popcll(__ballot(left != 0u));
-  }
-  if (lane == 0) { s_cnt[0][wv] = nl; s_cnt[1][wv] = nv - nl; }
-  __syncthreads();
-  stamp_.probe(5);  // the split bins are in: pass 1 done
-  if (threadIdx.x == 0) {
-    int tl = 0, tr = 0;
-    for (int k = 0; k < kPW; ++k) { tl += s_cnt[0][k]; tr += s_cnt[1][k]; }
-    const unsigned long long c = atomicAdd(reinterpret_cast<unsigned long long*>(d.cursors + 2 * node),
-                                           ((unsigned long long)(uint32_t)tr << 32) | (uint32_t)tl);
-    s_base[0] = (int32_t)(uint32_t)c;
-    s_base[1] = (int32_t)(c >> 32);
-  }
-  __syncthreads();
-  stamp_.probe(6);  // the item's ranges are claimed
-  int bl = s_base[0], br = s_base[1];
-  for (int k = 0; k < wv; ++k) { bl += s_cnt[0][k]; br += s_cnt[1][k]; }
-  uint32_t pl_ = (uint32_t)(nstart + bl);
-  uint32_t pr_ = (uint32_t)(nstart + ncount - 1 - br);
-#pragma unroll
-  for (int k = 0; k < kSteps; ++k) {
-    const bool valid = r[k] >= 0;
-    const uint32_t left = (lbits >> k) & 1u;
-    const uint64_t lm = __ballot(left != 0u), vm = __ballot(valid);
-    const uint32_t rk_l = mask_rank(lm);
-    const uint32_t dst = rk_l + (left ? pl_ : pr_ - (uint32_t)lane);
-    if (valid) store_wt(nxt + dst, r[k], (d.wt & 2) != 0);
-    const uint32_t cl = (uint32_t)__popcll(lm);
-    pl_ += cl;
-    pr_ -= (uint32_t)__popcll(vm) - cl;
-  }
-}
+#include "gbdt_part.h"
 
 // ------------------------------------------------------------------------------------------
 // Host-side trainer context
@@ -3570,29 +2940,6 @@ COBALT_API int cobalt_gbdt_set_data(void* h, uint8_t* bins, const uint8_t* binsT
   return 0;
 }
 
-static void launch_eval_part(int steps, int mode, dim3 grid, size_t lds, hipStream_t stream, const GbdtDev& d,
-                             int parity, int64_t zero_next, int level, int chunk, int tree, const EvalSlots& es,
-                             uint32_t tag) {
-#define EP_LAUNCH(S, M) \
-  hipLaunchKernelGGL((k_eval_part<S, M>), grid, dim3(1024), lds, stream, d, parity, zero_next, level, chunk, tree, es, tag)
-  if (steps <= 4) {
-    switch (mode) {
-      case 0: EP_LAUNCH(4, 0); break;
-      case 1: EP_LAUNCH(4, 1); break;
-      default: EP_LAUNCH(4, 2); break;
-    }
-  } else if (steps <= 6 && mode <= 1) {  // (1.25M rows: 6144-row items; the 8-step form spills 2 VGPRs)
-    if (mode == 0) EP_LAUNCH(6, 0); else EP_LAUNCH(6, 1);
-  } else {
-    switch (mode) {
-      case 0: EP_LAUNCH(8, 0); break;
-      case 1: EP_LAUNCH(8, 1); break;
-      default: EP_LAUNCH(8, 2); break;
-    }
-  }
-#undef EP_LAUNCH
-}
-
 // Everything a grow call decides once, before its first launch (plan_grow); the enqueue functions only read it.
 struct GrowPlan {
   bool dp;         // any native communicator turns on the data-parallel protocol (a 1-rank one exercises it on 1 GPU)
@@ -3840,20 +3187,10 @@ static int enqueue_level(GbdtCtx* c, const GrowPlan& p, int t, int level, hipStr
       const int evals = ep_mode >= 2 ? (1 << level) : 0;  // the evaluator blocks come first
       launch_eval_part(steps, ep_mode, dim3(ubp + evals), ep_mode == 2 ? p.fused_lds : 0, stream, d, parity, zero_next,
                        level, chp, t, c->eval_slots, ++c->dec_tag);
-    } else if (p.part_pos && (1 << level) <= kPartPosNodes) {  // position-ordered blocks (k_part_pos)
-      // (the grid from the instantiation's rows per block: COBALT_PART_CHUNK may give 1-3 or 5-7 steps)
-      const int ps = steps <= 4 ? 4 : 8;
-      const dim3 pg(std::max(1, (int)ceil_div(d.n, (int64_t)16 * kWave * ps)));
-      if (ps == 4)
-        GLAUNCH("k_partition", (k_part_pos<4>), pg, dim3(16 * kWave), 0, stream, d, parity, zero_next, level);
-      else
-        GLAUNCH("k_partition", (k_part_pos<8>), pg, dim3(16 * kWave), 0, stream, d, parity, zero_next, level);
-    } else if (steps <= 4)
-      GLAUNCH("k_partition", (k_partition<16, 4>), dim3(ubp), dim3(16 * kWave), 0, stream, d, parity, zero_next, level,
-              chp);
-    else
-      GLAUNCH("k_partition", (k_partition<16, 8>), dim3(ubp), dim3(16 * kWave), 0, stream, d, parity, zero_next, level,
-              chp);
+    } else {  // position-ordered blocks (k_part_pos) while the level's nodes fit, else node-ordered items
+      c->d.seq = stamp_next(c, "k_partition");
+      launch_partition(p.part_pos && (1 << level) <= kPartPosNodes, steps, ubp, stream, d, parity, zero_next, level, chp);
+    }
   }
   d.ipc_epoch = 0;
   CK_LAUNCH();

@@ -4,11 +4,13 @@ For a table of small fits -- one per branch of the plan, at the smallest shape t
 ``cobalt_gbdt_plan`` values, the ordered launch names of tree 0 (``COBALT_STAMPS``) and the grown model's bytes
 (their length and SHA-256) equal ``tests/golden/grow_plan.json``. The golden was recorded on an MI355X from the
 commit BEFORE binning and the external-memory passes left gbdt.hip and the evaluation kernels got one selector
-(``GROW_PLAN_RECORD=1 pytest tests/test_gpu_grow_plan.py -m gpu`` rewrites it: only ever from a commit whose
+(the ``cu12`` / ``cu16`` cases: from the commit before the row partition moved to gbdt_part.h;
+``GROW_PLAN_RECORD=1 pytest tests/test_gpu_grow_plan.py -m gpu`` rewrites it: only ever from a commit whose
 trainer is known good). Integer histograms make the trees exact.
 
-The fits run in child processes, one per group of process-cached knobs (``COBALT_EVAL_PART`` is read once per
-process), each with its own timeout; the knobs read per grow call are switched between the fits of a child.
+The fits run in child processes, one per group of process-cached knobs (``COBALT_EVAL_PART`` and
+``COBALT_CU_BUDGET`` are read once per process), each with its own timeout; the knobs read per grow call are
+switched between the fits of a child.
 """
 import hashlib
 import json
@@ -58,8 +60,27 @@ CASES = {
     "f20_d6_ep0_pp0": ("ep0", 20, 6, 1000, {"env": {"COBALT_PART_POS": "0"}}),   # k_eval + k_partition
     "f20_d6_ep0_pp0_n70000": ("ep0", 20, 6, 70_000, {"env": {"COBALT_PART_POS": "0"}}),
     "f20_ipc_ep0": ("ep0", 20, 6, 1000, {"comm": "ipc"}),            # fused exchange in k_eval<false, true, true>
+    # The 5- to 8-step partition instantiations (every case above has chunk_part = 4096: 4 steps). With
+    # COBALT_CU_BUDGET below ceil(70000 / 4096) = 18 CUs chunk_part is 8192, and plan_grow's every-block rule
+    # (the smallest item from 4096 in 1024-row steps whose grid, items + 2^level, fits the CUs) gives:
+    #   16 CUs: 5120 rows at levels 0-1, 6144 at level 2 (k_eval_part<6, *>), none <= 8192 at levels 3-4
+    #   12 CUs: 7168 rows at levels 0-1 (k_eval_part<8, *>), none <= 8192 at levels 2-4
+    # and the levels without one run k_eval + k_part_pos<8> (8192 positions per block).
+    "f20_d6_n70000_cu16": ("cu16", 20, 6, 70_000, {}),               # k_eval_part<6, 0>, k_part_pos<8>
+    "f20_loopback_n70000_cu16": ("cu16", 20, 6, 70_000, {"comm": "loopback"}),   # k_eval_part<6, 1>, k_part_pos<8>
+    # (depth 6 on 16 CUs: the fused exchange's deepest grid, 32 blocks, is not resident -> the separate exchange)
+    "f20_ipc_n70000_cu16": ("cu16", 20, 6, 70_000, {"comm": "ipc"}),             # k_eval_part<6, 1>, k_part_pos<8>
+    # depth 5: the fused exchange, evaluator blocks with 2 << level extra blocks: 5120 / 6144 rows at levels 0 / 1,
+    # chunk_part's 8192 at levels 2-3 (mode 2 has no 6-step form)
+    "f20_d5_ipc_n70000_cu16": ("cu16", 20, 5, 70_000, {"comm": "ipc"}),          # k_eval_part<8, 2>
+    "f20_d6_n70000_cu12": ("cu12", 20, 6, 70_000, {}),               # k_eval_part<8, 0>, k_part_pos<8>
+    "f20_loopback_n70000_cu12": ("cu12", 20, 6, 70_000, {"comm": "loopback"}),   # k_eval_part<8, 1>, k_part_pos<8>
+    "f20_d6_ep0_n70000_cu16": ("cu16_ep0", 20, 6, 70_000, {}),       # k_eval + k_part_pos<8> at every level
+    "f20_d6_ep0_pp0_n70000_cu16": ("cu16_ep0", 20, 6, 70_000, {"env": {"COBALT_PART_POS": "0"}}),  # k_partition<8>
 }
-GROUP_ENV = {"main": {}, "ep0": {"COBALT_EVAL_PART": "0"}}
+# knobs cached per process: one child per group
+GROUP_ENV = {"main": {}, "ep0": {"COBALT_EVAL_PART": "0"}, "cu16": {"COBALT_CU_BUDGET": "16"},
+             "cu12": {"COBALT_CU_BUDGET": "12"}, "cu16_ep0": {"COBALT_CU_BUDGET": "16", "COBALT_EVAL_PART": "0"}}
 
 
 def _data(n, F):
