@@ -20,6 +20,8 @@ Commands mirror the reference's scripts:
             row to the cutoff (explain/recourse.py)
   scorecard fit a WoE points scorecard, the transparent challenger, on a CSV and score rows with it
             (models/scorecard.py)
+  corr      correlation matrix of a CSV's numeric columns with missing values, the pairs above a threshold and the
+            greedy collinearity screen (select/collinearity.py)
 
 The artifact store is ``--store`` or ``$COBALT_ARTIFACT_URI`` (a local directory or ``s3://bucket``).
 """
@@ -385,6 +387,51 @@ def cmd_scorecard(args) -> int:
     return 0
 
 
+def cmd_corr(args) -> int:
+    """The correlation matrix (select/collinearity.py) of the numeric columns of TRAIN.csv: the pairs with ``|r|``
+    at or above --threshold and the greedy screen on stdout, everything as ``correlation.json`` in --out. With
+    --label the screen keeps, of two correlated features, the one with the higher information value."""
+    import os
+
+    import pandas as pd
+    import torch
+
+    from .select.collinearity import correlation_matrix, drop_correlated
+
+    df = pd.read_csv(args.train)
+    if args.label and args.label not in df.columns:
+        raise SystemExit(f"{args.train} has no column {args.label!r}")
+    cols = [c for c in df.columns if c != args.label and pd.api.types.is_numeric_dtype(df[c])
+            and not pd.api.types.is_bool_dtype(df[c])]
+    if not cols:
+        raise SystemExit("no numeric feature column")
+    dev = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
+    X = df[cols].to_numpy(dtype="float32", na_value=float("nan"))
+    X = torch.as_tensor(X, device=dev) if str(dev).startswith("cuda") else X
+    rep = correlation_matrix(X, cols, method=args.method, missing=args.missing, min_periods=args.min_periods)
+    priority = None
+    if args.label:
+        from .monitor import information_value
+
+        iv = {r["feature"]: r["iv"] for r in information_value(X, df[args.label].to_numpy(dtype="float32"),
+                                                               feature_names=cols)}
+        priority = [iv[c] for c in cols]
+    screen = drop_correlated(rep, args.threshold, priority=priority)
+    pairs = rep.pairs(args.threshold)
+    for p in pairs:
+        print(f"{p['a']}\t{p['b']}\t{p['r']:+.6f}\t{p['n']}")
+    for d in screen.dropped:
+        print(f"[DROP] {d['feature']} (r = {d['r']:+.4f} with {d['by']})")
+    print(f"[INFO] kept {len(screen.kept)} of {len(cols)} features at |r| < {args.threshold:g}")
+    os.makedirs(args.out, exist_ok=True)
+    path = os.path.join(args.out, "correlation.json")
+    with open(path, "w") as fh:
+        json.dump({**rep.to_dict(), "threshold": args.threshold, "pairs": pairs, "screen": screen.to_dict(),
+                   "priority": None if priority is None else dict(zip(cols, map(float, priority)))}, fh)
+    print(f"[INFO] wrote {path}")
+    return 0
+
+
 def main(argv: list[str] | None = None) -> int:
     logging.basicConfig(level=logging.INFO, format="[%(levelname)s] %(message)s")
     p = argparse.ArgumentParser(prog="cobalt_smart_lender_ai_amd")
@@ -500,6 +547,15 @@ def main(argv: list[str] | None = None) -> int:
     s.add_argument("--base-points", type=float, default=600.0)
     s.add_argument("--base-odds", type=float, default=50.0, help="odds good:bad at --base-points")
     s.set_defaults(fn=cmd_scorecard)
+    s = sub.add_parser("corr", help="correlation matrix, correlated pairs and the collinearity screen of TRAIN.csv")
+    s.add_argument("train", help="CSV with the feature columns (and the label, with --label)")
+    s.add_argument("--method", default="pearson", choices=["pearson", "spearman"])
+    s.add_argument("--missing", default="pairwise", choices=["pairwise", "listwise"])
+    s.add_argument("--min-periods", type=int, default=1)
+    s.add_argument("--threshold", type=float, default=0.7, help="|r| from which two features count as collinear")
+    s.add_argument("--label", default=None, help="0/1 label column: the screen keeps the feature with the higher IV")
+    s.add_argument("--out", default="correlation", help="directory for correlation.json")
+    s.set_defaults(fn=cmd_corr)
     args = p.parse_args(argv)
     return args.fn(args)
 

@@ -75,3 +75,22 @@ def describe(df: pd.DataFrame, device=None) -> pd.DataFrame:
                         "min": np.where(cnt > 0, mn, np.nan), **q, "max": np.where(cnt > 0, mx, np.nan)},
                        index=num).T
     return out
+
+
+def correlation(df: pd.DataFrame, method: str = "pearson", min_periods: int = 1, device=None) -> pd.DataFrame:
+    """``df.corr(method, min_periods)`` on the numeric columns, with pairwise deletion of missing values
+    (``select.collinearity.correlation_matrix``): on a GPU the columns go to the device as float32 and the moments
+    come from one pass of the correlation kernel (at most 128 columns); on the CPU they stay float64. Spearman
+    ranks each column once over its own present values, which is pandas' answer when nothing is missing."""
+    from ..select.collinearity import correlation_matrix
+
+    dev = frame.resolve_device(device)
+    num = frame.numeric_columns(df)
+    if not num:
+        return pd.DataFrame()
+    if dev.type == "cuda":
+        X = frame.to_device(df, num, dev).to(torch.float32).t().contiguous()
+        rep = correlation_matrix(X, num, method=method, min_periods=min_periods)
+    else:
+        rep = correlation_matrix(df[num], None, method=method, min_periods=min_periods)
+    return rep.to_frame()

@@ -150,3 +150,25 @@ def scorecard_plot(sc, feature):
 
 def close(fig) -> None:
     plt.close(fig)
+
+
+def correlation_heatmap(report, top: int | None = None):
+    """The correlation matrix of a ``select.CorrelationReport`` as a heat map on [-1, 1] (undefined entries stay
+    blank); ``top`` keeps the features with the largest off-diagonal ``|r|``, in their column order."""
+    r = np.asarray(report.r, dtype=np.float64)
+    names = list(report.names)
+    if not names:
+        raise ValueError("nothing to draw")
+    if top is not None and top < len(names):
+        off = np.where(np.eye(len(names), dtype=bool) | ~np.isfinite(r), 0.0, np.abs(r))
+        keep = np.sort(np.argsort(-off.max(axis=1), kind="stable")[:top])
+        r, names = r[np.ix_(keep, keep)], [names[i] for i in keep]
+    side = max(4.0, 0.32 * len(names) + 2.0)
+    fig, ax = plt.subplots(figsize=(side + 1.0, side))
+    im = ax.imshow(np.ma.masked_invalid(r), vmin=-1.0, vmax=1.0, cmap="RdBu_r")
+    ax.set_xticks(range(len(names)), names, rotation=90, fontsize=7)
+    ax.set_yticks(range(len(names)), names, fontsize=7)
+    fig.colorbar(im, ax=ax, label=f"{report.method} r")
+    ax.set_title("Feature correlation")
+    fig.tight_layout()
+    return fig
