@@ -22,6 +22,8 @@ Commands mirror the reference's scripts:
             (models/scorecard.py)
   corr      correlation matrix of a CSV's numeric columns with missing values, the pairs above a threshold and the
             greedy collinearity screen (select/collinearity.py)
+  portfolio-loss  Monte-Carlo loss distribution of a CSV of PDs and exposures under the Gaussian-copula factor
+            model: expected loss, VaR, expected shortfall and the segments' share of the tail (portfolio/)
 
 The artifact store is ``--store`` or ``$COBALT_ARTIFACT_URI`` (a local directory or ``s3://bucket``).
 """
@@ -432,6 +434,43 @@ def cmd_corr(args) -> int:
     return 0
 
 
+def cmd_portfolio_loss(args) -> int:
+    """The loss distribution (portfolio/) of the book in SCORES.csv: ``summary()`` on stdout and the whole report
+    as ``portfolio_loss.json`` in --out. --lgd and --rho take a number or, for --lgd, a column name."""
+    import os
+
+    import pandas as pd
+    import torch
+
+    from .portfolio import simulate_losses
+
+    df = pd.read_csv(args.csv)
+    try:
+        lgd = float(args.lgd)
+    except ValueError:
+        lgd = None
+    for c in [args.pd, args.exposure] + ([args.lgd] if lgd is None else []) + \
+            [c for c in (args.segment, args.sector) if c]:
+        if c not in df.columns:
+            raise SystemExit(f"{args.csv} has no column {c!r}")
+    dev = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
+    rho = [float(v) for v in str(args.rho).split(",")]
+    rep = simulate_losses(df[args.pd].to_numpy(dtype="float64"), df[args.exposure].to_numpy(dtype="float64"),
+                          lgd if lgd is not None else df[args.lgd].to_numpy(dtype="float64"),
+                          rho=rho[0] if len(rho) == 1 else rho,
+                          sector=df[args.sector].to_numpy() if args.sector else None,
+                          segment=df[args.segment].to_numpy() if args.segment else None,
+                          n_scenarios=args.scenarios, seed=args.seed, unit=args.unit,
+                          quantiles=tuple(float(q) for q in args.quantiles.split(",")), device=dev)
+    print(rep.summary())
+    os.makedirs(args.out, exist_ok=True)
+    path = os.path.join(args.out, "portfolio_loss.json")
+    with open(path, "w") as fh:
+        json.dump(rep.to_dict(), fh)
+    print(f"[INFO] wrote {path}")
+    return 0
+
+
 def main(argv: list[str] | None = None) -> int:
     logging.basicConfig(level=logging.INFO, format="[%(levelname)s] %(message)s")
     p = argparse.ArgumentParser(prog="cobalt_smart_lender_ai_amd")
@@ -556,6 +595,21 @@ def main(argv: list[str] | None = None) -> int:
     s.add_argument("--label", default=None, help="0/1 label column: the screen keeps the feature with the higher IV")
     s.add_argument("--out", default="correlation", help="directory for correlation.json")
     s.set_defaults(fn=cmd_corr)
+    s = sub.add_parser("portfolio-loss", help="loss distribution, VaR and expected shortfall of a CSV of PDs and "
+                                              "exposures")
+    s.add_argument("csv", help="CSV with one row per loan")
+    s.add_argument("--pd", default="pd", help="column of calibrated default probabilities")
+    s.add_argument("--exposure", default="loan_amnt", help="column of exposures at default")
+    s.add_argument("--lgd", default="1.0", help="loss given default: a number or a column")
+    s.add_argument("--rho", default="0.15", help="asset correlation: a number, or one per sector separated by commas")
+    s.add_argument("--sector", default=None, help="column of integer sector ids (one factor each)")
+    s.add_argument("--segment", default=None, help="column to break the loss down by")
+    s.add_argument("--scenarios", type=int, default=10000)
+    s.add_argument("--seed", type=int, default=0)
+    s.add_argument("--unit", type=int, default=100, help="integer units per currency unit (100: cents)")
+    s.add_argument("--quantiles", default="0.95,0.99,0.999")
+    s.add_argument("--out", default=".", help="directory for portfolio_loss.json")
+    s.set_defaults(fn=cmd_portfolio_loss)
     args = p.parse_args(argv)
     return args.fn(args)
 

@@ -172,3 +172,23 @@ def correlation_heatmap(report, top: int | None = None):
     ax.set_title("Feature correlation")
     fig.tight_layout()
     return fig
+
+
+def loss_distribution_plot(report, bins: int = 60):
+    """The scenario losses of a ``portfolio.LossReport`` as a histogram, with the expected loss and, at the
+    report's highest quantile, the value-at-risk and the expected shortfall marked."""
+    losses = np.asarray(report.losses, dtype=np.float64)
+    if losses.size == 0:
+        raise ValueError("nothing to draw")
+    k = repr(float(report.quantiles[-1]))
+    fig, ax = plt.subplots(figsize=(7, 4))
+    ax.hist(losses, bins=bins, color="#999999", edgecolor="white")
+    ax.axvline(report.expected_loss, color="#377eb8", lw=1.5, label=f"EL {report.expected_loss:,.0f}")
+    ax.axvline(report.var[k], color="#ff7f00", lw=1.5, ls="--", label=f"VaR {k} {report.var[k]:,.0f}")
+    ax.axvline(report.es[k], color="#e41a1c", lw=1.5, ls=":", label=f"ES {k} {report.es[k]:,.0f}")
+    ax.set_xlabel("Portfolio loss")
+    ax.set_ylabel("Scenarios")
+    ax.set_title(f"Loss distribution: {report.n_loans} loans, {report.n_scenarios} scenarios")
+    ax.legend(loc="upper right")
+    fig.tight_layout()
+    return fig
