@@ -24,6 +24,8 @@ Commands mirror the reference's scripts:
             greedy collinearity screen (select/collinearity.py)
   portfolio-loss  Monte-Carlo loss distribution of a CSV of PDs and exposures under the Gaussian-copula factor
             model: expected loss, VaR, expected shortfall and the segments' share of the tail (portfolio/)
+  fairness  fair-lending audit of a CSV of scores and protected attributes: adverse impact ratio, score and
+            error-rate gaps per group against a reference group, with bootstrap intervals (fairness/)
 
 The artifact store is ``--store`` or ``$COBALT_ARTIFACT_URI`` (a local directory or ``s3://bucket``).
 """
@@ -471,6 +473,36 @@ def cmd_portfolio_loss(args) -> int:
     return 0
 
 
+def cmd_fairness(args) -> int:
+    """The fair-lending audit (fairness/) of SCORES.csv: ``summary()`` on stdout and the whole report as JSON in
+    --out. Every --group column is one audited attribute; its values are read as strings."""
+    import pandas as pd
+    import torch
+
+    from .fairness import fair_lending_audit
+
+    df = pd.read_csv(args.csv)
+    for c in [args.score] + list(args.group) + ([args.label] if args.label else []):
+        if c not in df.columns:
+            raise SystemExit(f"{args.csv} has no column {c!r}")
+    dev = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
+    score = df[args.score].to_numpy(dtype="float32")
+    y = df[args.label].to_numpy(dtype="int64") if args.label else None
+    if str(dev).startswith("cuda"):
+        score = torch.as_tensor(score, device=dev)
+        y = None if y is None else torch.as_tensor(y, device=dev)
+    groups = {c: df[c].astype(str).to_numpy() for c in args.group}
+    reference = {c: args.reference for c in args.group} if args.reference is not None else None
+    cutoffs = [float(v) for v in args.cutoffs.split(",")] if args.cutoffs else None
+    rep = fair_lending_audit(score, groups, y, cutoff=args.cutoff, reference=reference, cutoffs=cutoffs,
+                             n_boot=args.n_boot, alpha=args.alpha, seed=args.seed, air_floor=args.air_floor)
+    print(rep.summary())
+    with open(args.out, "w") as fh:
+        json.dump(rep.to_dict(), fh)
+    print(f"[INFO] wrote {args.out}")
+    return 0
+
+
 def main(argv: list[str] | None = None) -> int:
     logging.basicConfig(level=logging.INFO, format="[%(levelname)s] %(message)s")
     p = argparse.ArgumentParser(prog="cobalt_smart_lender_ai_amd")
@@ -610,6 +642,20 @@ def main(argv: list[str] | None = None) -> int:
     s.add_argument("--quantiles", default="0.95,0.99,0.999")
     s.add_argument("--out", default=".", help="directory for portfolio_loss.json")
     s.set_defaults(fn=cmd_portfolio_loss)
+    s = sub.add_parser("fairness", help="fair-lending audit of a CSV of scores and protected attributes")
+    s.add_argument("csv", help="CSV with one row per applicant")
+    s.add_argument("--score", default="score", help="column of default probabilities")
+    s.add_argument("--group", action="append", required=True, help="protected-attribute column (repeatable)")
+    s.add_argument("--label", default=None, help="0/1 outcome column (1 = bad): adds error gaps, calibration, AUC")
+    s.add_argument("--cutoff", type=float, default=0.5, help="declined above this probability of default")
+    s.add_argument("--cutoffs", default=None, help="comma-separated further cutoffs for the AIR curve")
+    s.add_argument("--reference", default=None, help="reference group (default: the highest approval rate)")
+    s.add_argument("--n-boot", type=int, default=1000)
+    s.add_argument("--alpha", type=float, default=0.05)
+    s.add_argument("--seed", type=int, default=0)
+    s.add_argument("--air-floor", type=float, default=0.8)
+    s.add_argument("--out", default="fairness.json", help="where the report is written")
+    s.set_defaults(fn=cmd_fairness)
     args = p.parse_args(argv)
     return args.fn(args)
 

@@ -192,3 +192,51 @@ def loss_distribution_plot(report, bins: int = 60):
     ax.legend(loc="upper right")
     fig.tight_layout()
     return fig
+
+
+def adverse_impact_plot(report, attribute: str | None = None):
+    """The adverse impact ratio of every group of a ``fairness.FairnessReport`` with its bootstrap interval, and
+    the four-fifths floor as a line; ``attribute`` keeps one attribute. Groups below the floor with their whole
+    interval are red, those whose interval holds the floor orange."""
+    rows = [r for r in report.table() if attribute is None or r["attribute"] == attribute]
+    if not rows:
+        raise ValueError("nothing to draw")
+    colour = {"adverse": "#e41a1c", "inconclusive": "#ff7f00", "pass": "#377eb8"}
+    labels = [r["group"] if len(report.attributes) == 1 else f"{r['attribute']}: {r['group']}" for r in rows]
+    fig, ax = plt.subplots(figsize=(7, max(2.5, 0.4 * len(rows) + 1.2)))
+    for i, r in enumerate(rows):
+        air = np.nan if r["air"] is None else r["air"]
+        lo = air if r["air_low"] is None else r["air_low"]
+        hi = air if r["air_high"] is None else r["air_high"]
+        ax.errorbar(air, i, xerr=[[air - lo], [hi - air]], fmt="o", color=colour[r["verdict"]], capsize=3)
+    ax.axvline(report.air_floor, color="#444444", lw=1.0, ls="--", label=f"floor {report.air_floor:g}")
+    ax.set_yticks(range(len(rows)), labels)
+    ax.invert_yaxis()
+    ax.set_xlabel("Adverse impact ratio (approval rate over the reference's)")
+    ax.set_title(f"Adverse impact at cutoff {report.cutoff:g}")
+    ax.legend(loc="best")
+    fig.tight_layout()
+    return fig
+
+
+def air_curve_plot(report, attribute: str | None = None):
+    """The adverse impact ratio of every group of a ``fairness.FairnessReport`` over the cutoff grid, with its
+    bootstrap band and the floor line; ``attribute`` picks the attribute (default: the first)."""
+    name = attribute if attribute is not None else next(iter(report.attributes))
+    rows = [r for r in report.air_curve() if r["attribute"] == name]
+    if not rows:
+        raise ValueError("nothing to draw: the report has no cutoff grid")
+    fig, ax = plt.subplots(figsize=(7, 4))
+    for g in dict.fromkeys(r["group"] for r in rows):
+        pts = sorted((r for r in rows if r["group"] == g), key=lambda r: r["cutoff"])
+        x = [r["cutoff"] for r in pts]
+        as_float = lambda k: np.array([np.nan if r[k] is None else r[k] for r in pts], dtype=np.float64)  # noqa: E731
+        line, = ax.plot(x, as_float("air"), marker="o", ms=3, label=g)
+        ax.fill_between(x, as_float("low"), as_float("high"), color=line.get_color(), alpha=0.15)
+    ax.axhline(report.air_floor, color="#444444", lw=1.0, ls="--")
+    ax.set_xlabel("Cutoff (declined above it)")
+    ax.set_ylabel("Adverse impact ratio")
+    ax.set_title(f"Adverse impact over the cutoff: {name}")
+    ax.legend(loc="best", fontsize=8)
+    fig.tight_layout()
+    return fig
